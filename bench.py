@@ -15,7 +15,14 @@ locality) and uploads only the granules its tiles touch; no data-path
 collective.  Total work is fixed as N grows: "scaling": "strong", `value` =
 all 4096 tiles' output pixels / max-over-ranks time.
 
-The same line carries the other BASELINE configs under "configs" (each timed
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the
+headline needs: it sets the C2 batch up, warms up, times the N steps, writes
+the last step's output when `--dump-outputs DIR` is given (a seeded pixel
+sample and every tile's channel sums, float32 / float64 .npy) and prints the
+line.  Everything below runs with `--full` only.
+
+With `--full` the line also carries C2's roofline, tile latencies, PNG encode
+and CPU baseline, and the other BASELINE configs under "configs" (each timed
 the same way: warmup, barrier + synchronize, K steps, max over ranks):
   C1  single 256^2 tile: GPU p50/p99 latency, CPU (oracle) p50/p99 beside it;
   C3  WCS 16384^2 float32 bilinear coverage, chunk rows sharded over ranks,
@@ -301,6 +308,41 @@ def oracle_render(O, cfg, threads):
     return orr(O, cfg, n_threads=threads)
 
 
+DUMP_LIMIT = 64 * 1000 * 1000   # bytes of .npy payload per --dump-outputs directory
+DUMP_PIXELS = 1 << 21           # RGBA pixels of the sample (32 MiB as float32)
+DUMP_SEED = 0x6773_6B79
+
+
+def sample_rgba(rgba, n_pixels: int = DUMP_PIXELS, seed: int = DUMP_SEED):
+    """What --dump-outputs keeps of an RGBA batch (n_tiles, H, W, 4) uint8:
+    the same seeded draw of pixels on every run -- their flat indices
+    (float64, exact) and RGBA values (float32) -- and every tile's four
+    channel sums (float64, exact), so a change anywhere in the batch shows."""
+    flat = rgba.reshape(-1, 4)
+    npx = flat.shape[0]
+    if npx <= n_pixels:
+        idx = np.arange(npx, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(seed).integers(0, npx, n_pixels, dtype=np.int64))
+    picks = flat[torch.from_numpy(idx).to(rgba.device)].to(torch.float32).cpu().numpy()
+    per_tile = rgba.reshape(rgba.shape[0], -1, 4)
+    sums = torch.cat([per_tile[t0:t0 + 256].sum(dim=1, dtype=torch.float64)
+                      for t0 in range(0, per_tile.shape[0], 256)]).cpu().numpy()
+    return {"rgba_sample": picks, "rgba_sample_pixel": idx.astype(np.float64), "rgba_tile_sums": sums}
+
+
+def dump_outputs(ctx, dirname: str, arrays) -> None:
+    """--dump-outputs: {name: float32 / float64 array} as DIR/<name>.npy
+    (DIR/<name>.rank<r>.npy for rank r of several: each holds its own tiles)."""
+    os.makedirs(dirname, exist_ok=True)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: more than %d bytes" % DUMP_LIMIT)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError("--dump-outputs: %s is %s" % (name, a.dtype))
+        np.save(os.path.join(dirname, name + ("" if ctx.world == 1 else ".rank%d" % ctx.rank) + ".npy"), a)
+
+
 # ---------------------------------------------------------------- C2 (headline)
 def run_c2(ctx: Ctx, args):
     full = synth.config_c2()
@@ -317,8 +359,29 @@ def run_c2(ctx: Ctx, args):
         torch.cuda.synchronize()
         if bb.status() != 0:
             raise RuntimeError("render status %d" % bb.status())
-    dt = ctx.timed(lambda: step_batch.render(sp, pal), args.steps, args.warmup)
+    last = [None]
+
+    def step():
+        last[0] = step_batch.render(sp, pal)
+    dt = ctx.timed(step, args.steps, args.warmup)
     total_px = full.out_pixels * args.steps
+    out = {
+        "value": round(total_px / dt / 1e6, 1), "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "step_ms": ctx.step_stats,
+        "config": {"workload": "C2: %d x 512x512 EPSG:3857 tiles from %d EPSG:3577 int16 4000x4000 granules, "
+                               "nearest, time-ordered merge + scale + palette" % (len(full.tiles), len(full.granules)),
+                   "tiles_per_step": len(full.tiles), "tiles_per_rank": len(ids), "pairs_rank0": batch.n_pairs,
+                   "parallelism": "tile blocks over %d rank(s) (contiguous, balanced by 1 + pairs per tile, "
+                                  "granules per rank)" % ctx.world,
+                   "pipeline": "%d chunks on 2 HIP streams (plan of chunk k+1 under render of chunk k)"
+                               % args.c2_chunks if args.c2_chunks > 1 else "one batch, one stream"}}
+    if args.dump_outputs:
+        # what the last timed step returned, before anything else renders
+        dump_outputs(ctx, args.dump_outputs, sample_rgba(last[0]))
+    last[0] = None
+    if not args.full:
+        del batch, step_batch, gs
+        return out
     plan_ms = event_ms(lambda: batch.render(sp, pal, phase=1), max(3, args.steps))
     render_ms = event_ms(lambda: batch.render(sp, pal, phase=2), max(3, args.steps))
     # algorithmic bytes of rank 0's launch: the distinct
@@ -337,9 +400,7 @@ def run_c2(ctx: Ctx, args):
     lat = tile_latency(ctx, cfg, gs, sp, pal, lat_ids, args.c2_lat_reps) if lat_ids else [float("nan")]
     emp_ids = [empty[k] for k in range(0, len(empty), max(1, len(empty) // 8))][:8]
     lat_e = tile_latency(ctx, cfg, gs, sp, pal, emp_ids, args.c2_lat_reps) if emp_ids else [float("nan")]
-    out = {
-        "value": round(total_px / dt / 1e6, 1), "ms_per_step": round(dt / args.steps * 1e3, 4),
-        "step_ms": ctx.step_stats,
+    out.update({
         "p50_tile_ms": round(float(np.percentile(lat, 50)), 4),
         "p99_tile_ms": round(float(np.percentile(lat, 99)), 4),
         "p50_timing": "C2 one-tile GetMap requests over tiles with >= 1 granule (%d of the %d such tiles, evenly "
@@ -348,13 +409,6 @@ def run_c2(ctx: Ctx, args):
         "p50_empty_tile_ms": round(float(np.percentile(lat_e, 50)), 4),
         "empty_tiles": "%d of the %d tiles have no granule (transparent RGBA, no pair planning); %d timed"
                        % (len(empty), len(ids), len(emp_ids)),
-        "config": {"workload": "C2: %d x 512x512 EPSG:3857 tiles from %d EPSG:3577 int16 4000x4000 granules, "
-                               "nearest, time-ordered merge + scale + palette" % (len(full.tiles), len(full.granules)),
-                   "tiles_per_step": len(full.tiles), "tiles_per_rank": len(ids), "pairs_rank0": batch.n_pairs,
-                   "parallelism": "tile blocks over %d rank(s) (contiguous, balanced by 1 + pairs per tile, "
-                                  "granules per rank)" % ctx.world,
-                   "pipeline": "%d chunks on 2 HIP streams (plan of chunk k+1 under render of chunk k)"
-                               % args.c2_chunks if args.c2_chunks > 1 else "one batch, one stream"},
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": pmc_traffic("render_c2")
                      if ctx.world == 1 else None,
@@ -365,7 +419,7 @@ def run_c2(ctx: Ctx, args):
                      "bytes": "distinct source elements the tiles' windows pick (gskyhip_render_touched) x 2 B "
                               "+ 4 B RGBA per output pixel; source_line_bytes: the 128-B lines holding them",
                      "lib_sha16": lib_sha()},
-    }
+    })
     if ctx.rank == 0 and args.png_tiles > 0:
         # EncodePNG's png.Encode (ogc_encoders.go:139) of rendered C2 tiles:
         # colour type + Go's filter rows and the deflate (LZ77 + per-tile Huffman codes) on the GPU, PNG framing on host threads
@@ -807,6 +861,8 @@ def run_dry(ctx: Ctx, args):
         raise SystemExit(3)   # a failing rank: the launcher must fail and stop the others
     x = torch.zeros(1 << 16)
     dt = ctx.timed(lambda: x.add_(1.0), args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(ctx, args.dump_outputs, {"dry_run": x.numpy()})
     return {"value": round(ctx.world * (1 << 16) * args.steps / dt / 1e6, 3),
             "ms_per_step": round(dt / args.steps * 1e3, 4), "dry_run": True, "ranks": ctx.ranks_seen(),
             "config": {"workload": "dry run: 65536-element add per rank (launcher test)"}}
@@ -817,7 +873,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--only", default="c2,c1,c3,c4,c5,svc", help="comma list of configs (c2 is the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: C2's roofline, tile latencies, PNG encode and CPU baseline, and the "
+                         "configs of --only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--only", default=None,
+                    help="with --full: comma list of configs (default c2,c1,c3,c4,c5,svc; c2 is the headline)")
     ap.add_argument("--svc-jobs", type=int, default=1024, help="service leg: C2 (tile, granule) requests per run")
     ap.add_argument("--svc-window-us", type=int, default=0,
                     help="service leg: gskyhipd batching window (taken only while a batch is on the GPU)")
@@ -841,7 +903,13 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--dry-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.only is None:
+        args.only = "c2,c1,c3,c4,c5,svc" if args.full else "c2"
     only = [s.strip().lower() for s in args.only.split(",") if s.strip()]
+    if not args.full and only != ["c2"]:
+        ap.error("--only %s needs --full (a plain run times the C2 headline alone)" % args.only)
     if args.no_c1 and "c1" in only:
         only.remove("c1")
     ctx = Ctx(dry_run=args.dry_run)

@@ -8,8 +8,9 @@ product to the restatement bit for bit.  The product's rasterizer (scanline
 fill as per-edge parity toggles, drill_geom.cpp) is a different algorithm from
 the oracle's (GDAL's sorted intersection spans); they agree on every polygon
 below, including the reference's own WPS acceptance geometries
-(tests/golden/wps_polygons.json.gz: 32 local-government areas of 359-16,922
+(tests/golden/wps_polygons.<k>.json.gz: 32 local-government areas of 359-16,922
 vertices, extracted from acceptance_tests/polygon_requests/*.xml)."""
+import glob
 import gzip
 import json
 import os
@@ -27,9 +28,14 @@ WPS_DATASETS = [("EPSG:4326", [112.0, 0.01, 0.0, -9.0, 0.0, -0.01], 4300, 3500),
 
 def wps_polygons():
     """{request file: GeoJSON geometry} of the reference's WPS acceptance requests."""
-    p = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wps_polygons.json.gz")
-    with gzip.open(p, "rt", encoding="utf-8") as f:
-        return json.load(f)
+    parts = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                                          "wps_polygons.*.json.gz")))
+    assert parts, "tests/golden/wps_polygons.<k>.json.gz missing"
+    out = {}
+    for p in parts:
+        with gzip.open(p, "rt", encoding="utf-8") as f:
+            out.update(json.load(f))
+    return out
 
 
 def feature(rings, multi=False):

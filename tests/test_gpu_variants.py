@@ -86,7 +86,7 @@ print(json.dumps(res))
 def test_ab_build_variants_match_oracle(knobs):
     lib = os.path.join(ROOT, "gsky_amd", "libgskyhip_ab.so")
     if not os.path.exists(lib):
-        pytest.skip("A/B build not present (make -C gsky_amd/csrc ab)")
+        pytest.fail("A/B build not present (build() makes it: make -C gsky_amd/csrc ab)")
     env = dict(os.environ, GSKYHIP_LIB="ab", **knobs)
     p = subprocess.run([sys.executable, "-c", CHILD % {"root": ROOT}], env=env, capture_output=True, text=True,
                        timeout=240, cwd=ROOT)
