@@ -279,6 +279,25 @@ __global__ __launch_bounds__(256, WPS) void render_bil_kernel(RenderArgs a, cons
       // the nodata test of a tap in float32 (exact: the band's nodata is a float32 value or NaN)
       const bool nd_f32 = !hnd || nd_nan || (double)(float)nd64 == nd64;
       const float ndf = (float)nd64;
+      if (!nd_f32) {
+        // A nodata that no float32 equals drops no tap, so a sample over taps
+        // that all hold (float)nodata is the merge nodata itself and has to
+        // come out as exactly that value, which fp32 weights miss by an ulp:
+        // bil_sample's fp64 expressions, one pixel at a time (rare bands).
+        const float *bandp = (const float *)uniform_ptr(e.band);
+#pragma unroll
+        for (int q = 0; q < kNnPx; q++) {
+          const int ic = ic0 + 64 * q;
+          bool ok = (unsigned)ic < (unsigned)lim;
+          double sx = 0.0, sy = 0.0;
+          ok = ok && lin_coords(*rr, pool, ok ? ic : 0, sx, sy);
+          float v = fillv, got;
+          if (ok && bil_sample<float>(bandp, bx, by, hnd, nd64, GSKYHIP_FLOAT32, sx, sy, got)) v = got;
+          const bool take = ((unsigned)ic < (unsigned)lim) & (v != nd) & (!fill_mode | (c[q] == nd));
+          c[q] = take ? v : c[q];
+        }
+        continue;
+      }
       if (kind == ROW_LINEAR) {   // HP pixels' taps in flight
         const double xs0 = rr->v[0], ys0 = rr->v[1], dX = rr->v[2], dY = rr->v[3];
 #pragma unroll
@@ -298,7 +317,7 @@ __global__ __launch_bounds__(256, WPS) void render_bil_kernel(RenderArgs a, cons
             allin = allin & (((unsigned)ic >= (unsigned)lim) |
                              (((unsigned)ixv[q] < (unsigned)(bx - 1)) & ((unsigned)iyv[q] < (unsigned)(by - 1))));
           }
-          if (nd_f32 && __all(allin)) {
+          if (__all(allin)) {
             // every sampled pixel of the wave has its 2x2 taps inside the band:
             // no -1 edge rule, no tap outside; the weights of four valid taps
             // sum to 1 within fp32 rounding, so the sample is accR unless a

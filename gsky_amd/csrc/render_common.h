@@ -294,6 +294,17 @@ __device__ __forceinline__ bool nn_fetch(const EntryD &e, double sx, double sy, 
   return true;
 }
 
+// One tap of a bilinear sample as a double.  A signed-byte band is a GDT_Byte
+// band to the warp kernel (PIXELTYPE=SIGNEDBYTE is metadata), so its taps
+// enter the sample -- and the nodata test -- as 0..255; gdal_copy_to(...,
+// GSKYHIP_SIGNEDBYTE) clamps the result to 0..255 and wraps it back
+// (warp.go:354-359).  Read as int8 the negative values all clamped to 0.
+template <typename T>
+__device__ __forceinline__ double bil_tap(T v) {
+  if constexpr (std::is_same<T, int8_t>::value) return (double)(uint8_t)v;
+  else return (double)v;
+}
+
 template <typename T>
 __device__ __forceinline__ bool bil_fetch(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
   int iSrcX = (int)floor(sx - 0.5);
@@ -309,7 +320,7 @@ __device__ __forceinline__ bool bil_fetch(const EntryD &e, double sx, double sy,
     const int xx = iSrcX + (k & 1), yy = iSrcY + (k >> 1);
     const double w = ((k & 1) ? (1.0 - rX) : rX) * ((k >> 1) ? (1.0 - rY) : rY);
     if (xx < 0 || xx >= e.band_x || yy < 0 || yy >= e.band_y) continue;
-    const double d = (double)band[(long)yy * e.band_x + xx];
+    const double d = bil_tap<T>(band[(long)yy * e.band_x + xx]);
     if (e.has_nodata && (d == e.nodata64 || (e.nodata64 != e.nodata64 && d != d))) continue;
     accDiv += w;
     accR += d * w;

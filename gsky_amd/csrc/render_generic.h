@@ -29,9 +29,12 @@ __device__ __forceinline__ Val load_val(const void *band, int src_dtype, long id
   }
   return o;
 }
-__device__ __forceinline__ double load_dbl(const void *band, int src_dtype, long idx, int signed_byte) {
+// One tap of a bilinear sample.  A signed-byte band is a GDT_Byte band to the
+// warp kernel (PIXELTYPE=SIGNEDBYTE is metadata): its taps enter the sample as
+// 0..255, like bil_tap() (render_common.h).
+__device__ __forceinline__ double load_dbl(const void *band, int src_dtype, long idx) {
   switch (src_dtype) {
-    case GSKYHIP_BYTE: return signed_byte ? (double)((const int8_t *)band)[idx] : (double)((const uint8_t *)band)[idx];
+    case GSKYHIP_BYTE: return (double)((const uint8_t *)band)[idx];
     case GSKYHIP_INT16: return ((const int16_t *)band)[idx];
     case GSKYHIP_UINT16: return ((const uint16_t *)band)[idx];
     case GSKYHIP_FLOAT32: return ((const float *)band)[idx];
@@ -57,7 +60,7 @@ __device__ __noinline__ Val bilinear_value(const PairPlan &pp, double sx, double
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     if (xs4[k] < 0 || xs4[k] >= pp.band_x || ys4[k] < 0 || ys4[k] >= pp.band_y) continue;
-    const double v = load_dbl(pp.band, pp.src_dtype, (long)ys4[k] * pp.band_x + xs4[k], pp.signed_byte);
+    const double v = load_dbl(pp.band, pp.src_dtype, (long)ys4[k] * pp.band_x + xs4[k]);
     if (pp.has_nodata && (v == pp.nodata || (pp.nodata != pp.nodata && v != v))) continue;
     accDiv += w4[k];
     accR += v * w4[k];

@@ -103,7 +103,7 @@ __device__ __forceinline__ bool bil_sample(const T *band, int bx, int by, bool h
     const int xx = iSrcX + (k & 1), yy = iSrcY + (k >> 1);
     const double w = ((k & 1) ? (1.0 - rX) : rX) * ((k >> 1) ? (1.0 - rY) : rY);
     if (xx < 0 || xx >= bx || yy < 0 || yy >= by) continue;
-    const double d = (double)((const GPTR(T))band)[(int64_t)yy * bx + xx];
+    const double d = bil_tap<T>(((const GPTR(T))band)[(int64_t)yy * bx + xx]);
     if (has_nodata && (d == nodata64 || (nodata64 != nodata64 && d != d))) continue;
     accDiv += w;
     accR += d * w;

@@ -65,3 +65,51 @@ def identity(a: np.ndarray, b: np.ndarray) -> float:
     else:
         eq = (a == b) | (np.isnan(a.astype(np.float64)) & np.isnan(b.astype(np.float64)))
     return float(eq.mean())
+
+
+def cast_cfg(cfg: synth.SynthConfig, dt):
+    """The same geometry with granule values cast to `dt` (nodata mapped)."""
+    nod = {np.uint8: 0.0, np.int8: -1.0, np.uint16: 0.0, np.float32: -999.0, np.int16: -999.0}[dt]
+    for g in cfg.granules:
+        v = g.data.astype(np.int64)
+        bad = v == -999
+        if dt == np.uint8:
+            v = v % 250 + 1
+        elif dt == np.int8:
+            v = v % 200 - 100
+        g.data = v.astype(dt)
+        g.data[bad] = nod
+        g.nodata = nod
+    return cfg
+
+
+def bilinear_tie_masks(O, cfg: synth.SynthConfig, eps: float = 2.0 ** -10, windows: bool = False):
+    """Per tile, the (h, w) mask of pixels where an integer bilinear result
+    may sit on a rounding tie: the oracle's warp of every stack entry with the
+    granule cast to float32 (which holds 8- and 16-bit integers exactly, so
+    the window is the unrounded sample) lies within `eps` of k + 0.5.  Only
+    there may floor(v + 0.5) of two correct fp64 evaluations differ, by 1.
+    windows=True: also the mask of each pair's own window, in pair order."""
+    geots = [bbox_to_geot(w, h, bb) for (bb, w, h) in cfg.tiles]
+    dst = O.crs(cfg.dst_srs)
+    gr = {}
+    masks, wins = [], []
+    for t, (bb, w, h) in enumerate(cfg.tiles):
+        m = np.zeros((h, w), bool)
+        for gi in cfg.pairs[t]:
+            g = cfg.granules[gi]
+            if g.namespace not in cfg.namespaces:
+                continue
+            if gi not in gr:
+                # a signed-byte band is sampled as the bytes 0..255 (GDT_Byte)
+                as_f32 = lambda a: (a.view(np.uint8) if a.dtype == np.int8 else a).astype(np.float32)
+                gr[gi] = O.make_granule(as_f32(g.data), g.geot, g.nodata if g.nodata is not None else -1e10,
+                                        [as_f32(o) for o in g.overviews])
+            arr, bbox, nd, _ = O.warp(gr[gi], O.crs(g.srs), dst, geots[t], w, h, 1)
+            a = arr.astype(np.float64)
+            tie = (np.abs(a - np.floor(a) - 0.5) <= eps) & (a != nd)
+            x0, y0, ww, hh = (int(v) for v in bbox)
+            m[y0:y0 + hh, x0:x0 + ww] |= tie
+            wins.append(tie)
+        masks.append(m)
+    return (masks, wins) if windows else masks
