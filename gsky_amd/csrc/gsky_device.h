@@ -1,6 +1,6 @@
 // gsky_device.h -- device-side building blocks of the MI355X raster hot path.
 //
-// Projection math restates PROJ 6.1.1 (merc/webmerc, aea, gn_sinu, tmerc, lcc, polar stere and the
+// Projection math restates PROJ 6.1.1 (merc/webmerc, aea, gn_sinu, tmerc, lcc, polar stere, geos and the
 // pj_fwd / pj_inv wrappers) and GDAL 3.0.1's GenImgProj transformer; numeric
 // conversions restate Go 1.12 on amd64.  All of it
 // is compiled with -ffp-contract=off so every double expression rounds once
@@ -334,6 +334,64 @@ __host__ __device__ inline __attribute__((noinline)) bool stere_inv(const gskyhi
   return false;
 }
 
+// Geostationary satellite view, ellipsoidal (PROJ 6.1.1 geos.cpp e_forward /
+// e_inverse, [ext]; with es == 0 the same expressions are its spherical
+// form).  In units of the semi-major axis: radius_g_1 = h / a in c.phi1,
+// the sweep flag (1: +sweep=x, GOES-R; 0: +sweep=y, Himawari / Meteosat) in
+// c.phi2, radius_g in c.n, C = radius_g^2 - 1 in c.c, radius_p in c.dd,
+// radius_p2 in c.rho0, radius_p_inv2 in c.ec.  Pinned by the GOES-R PUG worked
+// example and the CGMS LRIT/HRIT 4.4.3.2 formulation in tests/test_geos.py.
+// Out of line, transcendentals through ext_*, for the register reason above.
+__host__ __device__ inline __attribute__((noinline)) double ext_cos(double a) { return cos(a); }
+
+// false: the point is not visible from the satellite (beyond the limb).
+__host__ __device__ inline __attribute__((noinline)) bool geos_fwd(const gskyhip_crs &c, double lam, double phi,
+                                                                    double &xn, double &yn) {
+  phi = ext_atan(c.rho0 * ext_tan(phi));   // geocentric latitude
+  const double cphi = ext_cos(phi), sphi = ext_sin(phi);
+  // vector from the Earth's centre to the surface point
+  const double r = c.dd / hypot(c.dd * cphi, sphi);
+  const double Vx = r * ext_cos(lam) * cphi;
+  const double Vy = r * ext_sin(lam) * cphi;
+  const double Vz = r * sphi;
+  if (((c.n - Vx) * Vx - Vy * Vy - Vz * Vz * c.ec) < 0.) return false;
+  const double tmp = c.n - Vx;   // view angles from the satellite
+  if (c.phi2 != 0.) {
+    xn = c.phi1 * ext_atan(Vy / hypot(Vz, tmp));
+    yn = c.phi1 * ext_atan(Vz / tmp);
+  } else {
+    xn = c.phi1 * ext_atan(Vy / tmp);
+    yn = c.phi1 * ext_atan(Vz / hypot(Vy, tmp));
+  }
+  return true;
+}
+
+// false: the view ray misses the ellipsoid (space around the disc).
+__host__ __device__ inline __attribute__((noinline)) bool geos_inv(const gskyhip_crs &c, double xn, double yn,
+                                                                    double &lam, double &phi) {
+  double Vx = -1.0, Vy, Vz;
+  if (c.phi2 != 0.) {
+    Vz = ext_tan(yn / c.phi1);
+    Vy = ext_tan(xn / c.phi1) * hypot(1.0, Vz);
+  } else {
+    Vy = ext_tan(xn / c.phi1);
+    Vz = ext_tan(yn / c.phi1) * hypot(1.0, Vy);
+  }
+  double a = Vz / c.dd;
+  a = Vy * Vy + a * a + Vx * Vx;
+  const double b = 2 * c.n * Vx;
+  const double det = (b * b) - 4 * a * c.c;
+  if (!(det >= 0.)) return false;
+  const double k = (-b - sqrt(det)) / (2. * a);
+  Vx = c.n + k * Vx;
+  Vy *= k;
+  Vz *= k;
+  lam = atan2(Vy, Vx);
+  phi = ext_atan(Vz * ext_cos(lam) / Vx);
+  phi = ext_atan(c.ec * ext_tan(phi));
+  return true;
+}
+
 // pj_inv: CRS coordinates -> (lam, phi) in radians.
 __host__ __device__ inline bool crs_inverse(const gskyhip_crs &c, double x, double y, double &lam, double &phi) {
   if (x == HUGE_VAL || y == HUGE_VAL) return false;
@@ -381,6 +439,8 @@ __host__ __device__ inline bool crs_inverse(const gskyhip_crs &c, double x, doub
     if (!lcc_inv(c, xn, yn, l, p)) return false;
   } else if (c.kind == GSKYHIP_CRS_STERE_POLAR) {  // stere.cpp e_inverse (polar)
     if (!stere_inv(c, xn, yn, l, p)) return false;
+  } else if (c.kind == GSKYHIP_CRS_GEOS) {  // geos.cpp e_inverse
+    if (!geos_inv(c, xn, yn, l, p)) return false;
   } else {
     return false;
   }
@@ -425,6 +485,8 @@ __host__ __device__ inline bool crs_forward(const gskyhip_crs &c, double lam, do
     if (!lcc_fwd(c, lam, phi, xn, yn)) return false;
   } else if (c.kind == GSKYHIP_CRS_STERE_POLAR) {  // stere.cpp e_forward (polar)
     if (!stere_fwd(c, lam, phi, xn, yn)) return false;
+  } else if (c.kind == GSKYHIP_CRS_GEOS) {  // geos.cpp e_forward
+    if (!geos_fwd(c, lam, phi, xn, yn)) return false;
   } else {
     return false;
   }

@@ -187,6 +187,29 @@ int stere_polar_setup(gskyhip_crs *c, double phi0, bool has_ts, double lat_ts) {
   return 0;
 }
 
+// geos.cpp setup() of PROJ 6.1.1: the satellite height above the ellipsoid
+// and the sweep axis; constants in units of the semi-major axis, assigned as
+// gsky_device.h geos_fwd / geos_inv (and include/gskyhip.h) document.  A
+// sphere (es == 0) runs the same expressions with radius_p = 1.
+int geos_setup(gskyhip_crs *c, double h, bool sweep_x) {
+  if (!(h > 0.)) return GSKYHIP_E_CRS;
+  c->kind = GSKYHIP_CRS_GEOS;
+  c->phi0 = 0.0;
+  c->k0 = 1.0;
+  c->phi1 = h / c->a;                  // radius_g_1
+  c->phi2 = sweep_x ? 1.0 : 0.0;       // flip_axis
+  c->n = 1. + c->phi1;                 // radius_g
+  c->c = c->n * c->n - 1.0;            // C
+  if (c->es != 0.0) {
+    c->dd = std::sqrt(c->one_es);      // radius_p
+    c->rho0 = c->one_es;               // radius_p2
+    c->ec = 1. / c->one_es;            // radius_p_inv2
+  } else {
+    c->dd = c->rho0 = c->ec = 1.0;
+  }
+  return 0;
+}
+
 // utm.cpp setup: zone -> central meridian, k0 0.9996, false easting 500 km,
 // false northing 10,000 km in the south.
 int utm_setup(gskyhip_crs *c, int zone, bool south) {
@@ -307,6 +330,28 @@ int crs_proj4(const std::string &s, gskyhip_crs *c) {
     if (!has_k) c->k0 = proj_param(s, "+k", 1.0);
     return stere_polar_setup(c, c->phi0, has_ts, ts);
   }
+  if (s.find("+proj=geos") != std::string::npos) {   // geos.cpp: +h required and positive, +sweep x or y
+    set_ellps(c, a, rf);
+    bool has_b = false, has_h = false;
+    const double b = proj_param(s, "+b", 0, &has_b);
+    if (has_b && rf == 0 && !(R > 0)) {   // +a +b (the form satellite operators publish): es = 1 - b^2 / a^2
+      if (!(b > 0)) return GSKYHIP_E_CRS;
+      c->es = 1.0 - (b * b) / (a * a);
+      c->e = std::sqrt(c->es);
+      c->one_es = 1.0 - c->es;
+    }
+    const double h = proj_param(s, "+h", 0, &has_h);
+    if (!has_h) return GSKYHIP_E_CRS;
+    bool sweep_x = false;
+    const size_t sw = s.find("+sweep=");
+    if (sw != std::string::npos) {
+      const char ax = s[sw + 7];
+      const char nx = sw + 8 < s.size() ? s[sw + 8] : ' ';
+      if ((ax != 'x' && ax != 'y') || (nx != ' ' && nx != '\0')) return GSKYHIP_E_CRS;
+      sweep_x = ax == 'x';
+    }
+    return geos_setup(c, h, sweep_x);
+  }
   if (s.find("+proj=lcc") != std::string::npos) {   // lcc.cpp: one parallel -> the tangent cone at it
     set_ellps(c, a, rf);
     bool has_l1 = false, has_l2 = false, has_l0 = false, has_k = false;
@@ -338,7 +383,9 @@ int parse_srs(const char *srs, gskyhip_crs *c) {
   auto ieq = [](const std::string &a, const char *b) { return strcasecmp(a.c_str(), b) == 0; };
   if (ieq(s, "MODIS") || ieq(s, "SR-ORG:6842")) return crs_proj4("+proj=sinu +R=6371007.181", c);
   if (s.size() > 5 && strncasecmp(s.c_str(), "EPSG:", 5) == 0) return crs_epsg(std::atoi(s.c_str() + 5), c);
-  if (s.find("+proj=") != std::string::npos) return crs_proj4(s, c);
+  // (a WKT1 Geostationary_Satellite node may carry a PROJ string in its EXTENSION: parsed as WKT below)
+  if (s.find("+proj=") != std::string::npos && s.find("PROJECTION[\"Geostationary_Satellite\"]") == std::string::npos)
+    return crs_proj4(s, c);
   // WKT: a Sinusoidal / Lambert Conformal Conic / Transverse Mercator projection, else the top-level (last) EPSG
   // authority
   if (s.find("PROJECTION[\"Sinusoidal\"]") != std::string::npos) {
@@ -377,6 +424,38 @@ int parse_srs(const char *srs, gskyhip_crs *c) {
     c->y0 = param("false_northing", 0);
     return stere_polar_setup(c, (ts < 0 ? -90.0 : 90.0) * kD2R_h, std::fabs(std::fabs(ts) - 90.0) > 1e-12,
                              ts * kD2R_h);
+  }
+  if (s.find("PROJECTION[\"Geostationary_Satellite\"]") != std::string::npos) {   // WKT1 (GDAL)
+    auto param = [&](const char *name, double dflt) {
+      const std::string k = std::string("PARAMETER[\"") + name + "\",";
+      const size_t p = s.find(k);
+      return p == std::string::npos ? dflt : std::strtod(s.c_str() + p + k.size(), nullptr);
+    };
+    double a = 6378137.0, rf = 298.257223563;
+    const size_t p = s.find("SPHEROID[");
+    if (p != std::string::npos) {
+      const size_t q = s.find(',', p);
+      if (q != std::string::npos) {
+        char *end = nullptr;
+        a = std::strtod(s.c_str() + q + 1, &end);
+        if (end && *end == ',') rf = std::strtod(end + 1, nullptr);
+      }
+    }
+    std::memset(c, 0, sizeof(*c));
+    set_ellps(c, a, rf);
+    c->lam0 = param("central_meridian", 0) * kD2R_h;
+    c->x0 = param("false_easting", 0);
+    c->y0 = param("false_northing", 0);
+    // WKT1 has no sweep parameter: GDAL carries +sweep=x in an
+    // EXTENSION["PROJ4", "... +sweep=x ..."] node
+    bool sweep_x = false;
+    const size_t ext = s.find("EXTENSION[\"PROJ4\"");
+    if (ext != std::string::npos) {
+      const size_t close = s.find(']', ext);
+      const size_t sw = s.find("+sweep=x", ext);
+      sweep_x = sw != std::string::npos && (close == std::string::npos || sw < close);
+    }
+    return geos_setup(c, param("satellite_height", 0), sweep_x);
   }
   const bool lcc2 = s.find("PROJECTION[\"Lambert_Conformal_Conic_2SP\"]") != std::string::npos;
   const bool lcc1 = s.find("PROJECTION[\"Lambert_Conformal_Conic_1SP\"]") != std::string::npos;

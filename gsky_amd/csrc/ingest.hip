@@ -43,6 +43,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <strings.h>
 #include <thread>
 #include <vector>
 
@@ -1026,6 +1027,26 @@ int nc_epsg(const Nc &f, const NcVar &v) {
   return 0;
 }
 
+// perspective_point_height where the CF geostationary mapping omits it
+// (netcdfdataset.cpp:3147)
+constexpr double kGeosDefaultH = 35785831.0;
+
+// True, with the satellite height, when the variable's grid mapping is the CF
+// geostationary one: its x / y axes may then be scan angles (nc_fill_info).
+bool nc_geos_height(const Nc &f, const NcVar &v, double &h) {
+  const NcAtt *gm = nc_att(v.atts, "grid_mapping");
+  if (!gm) return false;
+  for (const NcVar &m : f.vars) {
+    if (m.name != std::string(gm->text.c_str())) continue;
+    const NcAtt *gn = nc_att(m.atts, "grid_mapping_name");
+    if (!gn || strcasecmp(gn->text.c_str(), "geostationary") != 0) return false;
+    const NcAtt *a = nc_att(m.atts, "perspective_point_height");
+    h = (a && !a->num.empty()) ? a->num[0] : kGeosDefaultH;
+    return true;
+  }
+  return false;
+}
+
 // The SRS of the variable's CF grid mapping (grid_mapping_name and its
 // parameters, CF-1.x Appendix F, as GSKY_netCDF's SetProjectionFromVar reads
 // them), as a PROJ string of the projection families the warp supports;
@@ -1125,6 +1146,14 @@ std::string nc_cf_srs(const Nc &f, const NcVar &v) {
                         lat0, cm, num(m, "scale_factor_at_projection_origin", 0, 1.0), fe, fn, ell);
         return buf;
       }
+      if (name == "geostationary") {   // netcdfdataset.cpp:3139-3175; ellipsoid or sphere
+        const NcAtt *sw = nc_att(m.atts, "sweep_angle_axis");
+        const bool sweep_x = sw && strcasecmp(sw->text.c_str(), "x") == 0;   // anything else, or absent: y
+        std::snprintf(buf, sizeof(buf), "+proj=geos +lon_0=%.17g +h=%.17g +x_0=%.17g +y_0=%.17g %s +sweep=%s",
+                      num(m, "longitude_of_projection_origin", 0, 0), num(m, "perspective_point_height", 0, kGeosDefaultH),
+                      fe, fn, ell, sweep_x ? "x" : "y");
+        return buf;
+      }
       if (name == "sinusoidal" && sphere) {
         std::snprintf(buf, sizeof(buf), "+proj=sinu +lon_0=%.17g +x_0=%.17g +y_0=%.17g %s",
                       num(m, "longitude_of_central_meridian", 0, num(m, "longitude_of_projection_origin", 0, 0)),
@@ -1175,6 +1204,8 @@ int nc_fill_info(const NcRaster &r, gskyhip_raster_info *info) {
   g[0] = 0; g[1] = 1; g[2] = 0; g[3] = 0; g[4] = 0; g[5] = 1;
   const size_t nd = v.dims.size();
   const Nc &f = r.f;
+  double geos_h = 0;
+  const bool geos = nc_geos_height(f, v, geos_h);
   auto coord = [&](const std::string &dn, int64_t n, double mm[2]) {
     for (const NcVar &cv : f.vars)
       if (cv.name == dn && cv.dims.size() == 1 && !cv.record) {
@@ -1186,6 +1217,19 @@ int nc_fill_info(const NcRaster &r, gskyhip_raster_info *info) {
         if (ao && sf && !ao->num.empty() && !sf->num.empty()) {
           mm[0] = ao->num[0] + mm[0] * sf->num[0];
           mm[1] = ao->num[0] + mm[1] * sf->num[0];
+        }
+        // a geostationary grid's axes may be scan angles: to metres by the
+        // satellite height, per axis, after scale / offset (netcdfdataset.cpp:3578-3626)
+        if (geos) {
+          const NcAtt *un = nc_att(cv.atts, "units");
+          const char *u = un ? un->text.c_str() : "";
+          if (strcasecmp(u, "microradian") == 0) {
+            mm[0] = mm[0] * geos_h * 0.000001;
+            mm[1] = mm[1] * geos_h * 0.000001;
+          } else if (strcasecmp(u, "rad") == 0) {
+            mm[0] = mm[0] * geos_h;
+            mm[1] = mm[1] * geos_h;
+          }
         }
         return true;
       }

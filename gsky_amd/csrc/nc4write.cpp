@@ -257,13 +257,18 @@ uint64_t chunk_btree(Img &img, const std::vector<ChunkRec> &chunks, uint64_t n_r
 
 // ---------------------------------------------------------------- CRS
 // CF grid-mapping attributes of the SRS of `epsg` (CF-1.x Appendix F), the
-// family set the warp supports; false when the code is outside it.
-bool cf_mapping(int epsg, std::vector<Att> &atts, bool &geographic) {
+// family set the warp supports; false when the code is outside it.  `srs_in`
+// (may be NULL) replaces the code for an SRS without one (the geostationary
+// family); `c` receives the parsed CRS.
+bool cf_mapping(int epsg, const char *srs_in, std::vector<Att> &atts, bool &geographic, gskyhip_crs &c) {
   char srs[32];
   std::snprintf(srs, sizeof(srs), "EPSG:%d", epsg);
-  gskyhip_crs c;
   geographic = false;
-  if (epsg <= 0 || gskyhip_crs_from_srs(srs, &c) != 0) return false;
+  if (srs_in && *srs_in) {
+    if (gskyhip_crs_from_srs(srs_in, &c) != 0) return false;
+  } else if (epsg <= 0 || gskyhip_crs_from_srs(srs, &c) != 0) {
+    return false;
+  }
   const double rad = 180.0 / M_PI;
   auto ellps = [&]() {
     if (c.es == 0.0) {
@@ -332,6 +337,15 @@ bool cf_mapping(int epsg, std::vector<Att> &atts, bool &geographic) {
       atts.push_back(att_f64("false_northing", {c.y0}));
       ellps();
       return true;
+    case GSKYHIP_CRS_GEOS:   // sweep_angle_axis always written (netcdfdataset.cpp:4192-4200)
+      atts.push_back(att_str("grid_mapping_name", "geostationary"));
+      atts.push_back(att_f64("longitude_of_projection_origin", {c.lam0 * rad}));
+      atts.push_back(att_f64("perspective_point_height", {c.phi1 * c.a}));
+      atts.push_back(att_str("sweep_angle_axis", c.phi2 != 0.0 ? "x" : "y"));
+      atts.push_back(att_f64("false_easting", {c.x0}));
+      atts.push_back(att_f64("false_northing", {c.y0}));
+      ellps();
+      return true;
     default:
       return false;
   }
@@ -384,8 +398,9 @@ extern "C" int64_t gskyhip_netcdf_bound(int width, int height, int n_bands, int 
 // The file from host bands (each height x width of dtype, row-major; NULL or
 // an "EmptyTile" name: a skipped band of zeros).
 static int encode_netcdf_host(const void *const *bands, int n_bands, int dtype, int width, int height,
-                              const double *geot, int epsg, const double *nodata, const char *const *names, int zlevel,
-                              int n_threads, uint8_t *out, int64_t capacity, int64_t *size) {
+                              const double *geot, int epsg, const char *srs, const double *nodata,
+                              const char *const *names, int zlevel, int n_threads, uint8_t *out, int64_t capacity,
+                              int64_t *size) {
   char kind;
   int es;
   bool unsigned_att;
@@ -416,7 +431,9 @@ static int encode_netcdf_host(const void *const *bands, int n_bands, int dtype, 
   }
   std::vector<Att> crs_atts;
   bool geographic = false;
-  const bool have_crs = cf_mapping(epsg, crs_atts, geographic);
+  gskyhip_crs crs;
+  std::memset(&crs, 0, sizeof(crs));
+  const bool have_crs = cf_mapping(epsg, srs, crs_atts, geographic, crs);
 
   Img img;
   img.reserve(48);   // superblock 2
@@ -481,9 +498,21 @@ static int encode_netcdf_host(const void *const *bands, int n_bands, int dtype, 
     Bytes lay;
     lay.u8(3).u8(1).u64(kUndef).u64(4);   // contiguous, not allocated: reads as the fill
     msgs.push_back({0x08, lay});
-    char wkt[160], gts[256];
-    std::snprintf(wkt, sizeof(wkt), "%s[\"EPSG:%d\",AUTHORITY[\"EPSG\",\"%d\"]]", geographic ? "GEOGCS" : "PROJCS", epsg,
-                  epsg);
+    char wkt[768], gts[256];
+    if (crs.kind == GSKYHIP_CRS_GEOS) {   // no EPSG code: the WKT1 projection node with its parameters
+      const double f = 1.0 - std::sqrt(1.0 - crs.es);
+      std::snprintf(wkt, sizeof(wkt),
+                    "PROJCS[\"unnamed\",GEOGCS[\"unknown\",DATUM[\"unknown\",SPHEROID[\"unknown\",%.17g,%.17g]],"
+                    "PRIMEM[\"Greenwich\",0],UNIT[\"degree\",0.0174532925199433]],"
+                    "PROJECTION[\"Geostationary_Satellite\"],PARAMETER[\"central_meridian\",%.17g],"
+                    "PARAMETER[\"satellite_height\",%.17g],PARAMETER[\"false_easting\",%.17g],"
+                    "PARAMETER[\"false_northing\",%.17g],UNIT[\"metre\",1]%s]",
+                    crs.a, f == 0.0 ? 0.0 : 1.0 / f, crs.lam0 * (180.0 / M_PI), crs.phi1 * crs.a, crs.x0, crs.y0,
+                    crs.phi2 != 0.0 ? ",EXTENSION[\"PROJ4\",\"+sweep=x\"]" : "");
+    } else {
+      std::snprintf(wkt, sizeof(wkt), "%s[\"EPSG:%d\",AUTHORITY[\"EPSG\",\"%d\"]]", geographic ? "GEOGCS" : "PROJCS",
+                    epsg, epsg);
+    }
     std::snprintf(gts, sizeof(gts), "%.17g %.17g %.17g %.17g %.17g %.17g", geot[0], geot[1], geot[2], geot[3], geot[4],
                   geot[5]);
     crs_atts.push_back(att_str("spatial_ref", wkt));
@@ -621,7 +650,18 @@ extern "C" int gskyhip_encode_netcdf_host(const void *const *bands, int n_bands,
                                           const double *geot, int epsg, const double *nodata,
                                           const char *const *names, int zlevel, int n_threads, uint8_t *out,
                                           int64_t capacity, int64_t *size) {
-  return encode_netcdf_host(bands, n_bands, dtype, width, height, geot, epsg, nodata, names, zlevel, n_threads, out,
+  return encode_netcdf_host(bands, n_bands, dtype, width, height, geot, epsg, nullptr, nodata, names, zlevel, n_threads,
+                            out, capacity, size);
+}
+
+extern "C" int gskyhip_encode_netcdf_srs_host(const void *const *bands, int n_bands, int dtype, int width, int height,
+                                              const double *geot, const char *srs, const double *nodata,
+                                              const char *const *names, int zlevel, int n_threads, uint8_t *out,
+                                              int64_t capacity, int64_t *size) {
+  if (!srs || !*srs) return GSKYHIP_E_ARG;
+  gskyhip_crs c;
+  if (gskyhip_crs_from_srs(srs, &c) != 0) return GSKYHIP_E_CRS;
+  return encode_netcdf_host(bands, n_bands, dtype, width, height, geot, 0, srs, nodata, names, zlevel, n_threads, out,
                             capacity, size);
 }
 
@@ -642,6 +682,6 @@ extern "C" int gskyhip_encode_netcdf(const void *const *bands, int n_bands, int 
     ptrs[k] = host[k].data();
   }
   if (hipStreamSynchronize(s) != hipSuccess) return GSKYHIP_E_HIP;
-  return encode_netcdf_host(ptrs.data(), n_bands, dtype, width, height, geot, epsg, nodata, names, zlevel, n_threads,
-                            out, capacity, size);
+  return encode_netcdf_host(ptrs.data(), n_bands, dtype, width, height, geot, epsg, nullptr, nodata, names, zlevel,
+                            n_threads, out, capacity, size);
 }

@@ -588,6 +588,29 @@ __device__ int suggested_warp_output2_blk(const Xform &t, int nInX, int nInY, do
   return err;
 }
 
+// Geostationary sources only (the one family whose valid domain ends at a
+// failure, not at the granule's outline): true when some sample of the
+// 21 x 21 source grid lies on the disc at a longitude beyond +-180 degrees,
+// i.e. the part of the disc the granule holds crosses the antimeridian and
+// PROJ wraps those samples to the other end of a cylindrical destination.
+// By the whole workgroup of NT threads.
+template <int NT>
+__device__ __attribute__((noinline)) int geos_seam(const Xform &t, int nInX, int nInY) {
+  int hit = 0;
+  for (int k = threadIdx.x; k < kGrid; k += NT) {
+    const int iy = k / (kSteps + 1), ix = k % (kSteps + 1);
+    const double x = ((ix == kSteps) ? 1.0 : ix * (1.0 / kSteps)) * nInX;
+    const double y = ((iy == kSteps) ? 1.0 : iy * (1.0 / kSteps)) * nInY;
+    const double X = t.src_gt[0] + x * t.src_gt[1] + y * t.src_gt[2];
+    const double Y = t.src_gt[3] + x * t.src_gt[4] + y * t.src_gt[5];
+    double l, p;
+    if (geos_inv(t.src, (X - t.src.x0) * t.src.ra, (Y - t.src.y0) * t.src.ra, l, p) &&
+        fabs(l + t.src.lam0) >= kPi + 1e-12)
+      hit = 1;
+  }
+  return __syncthreads_or(hit);
+}
+
 // Plan of pair p by one workgroup of NT threads (sx / sy / sok: LDS scratch
 // of kGrid entries, ts: the transformer in LDS).
 template <int NT>
@@ -660,6 +683,25 @@ __device__ void plan_pair(const PlanArgs &a, int p, double *sx, double *sy, int 
     err = suggested_warp_output2_blk<NT>(t, nInX, nInY, sx, sy, sok, ext, psx, psy, nPixels, nLines,
                                          a.gedge ? a.gedge + gi : nullptr, ps);
   PSTAMP(ps, 5);
+  // A geostationary disc across the antimeridian, into a cylindrical north-up
+  // destination (workgroup-uniform test): the wrapped samples put the
+  // extent's ends within a sample spacing of the destination's periodic
+  // edges; GDAL stops there, which leaves the columns between the edge and
+  // the first wrapped sample -- ground well inside the disc -- out of the
+  // window (a nodata seam along +-180 in world tiles).  Deliberately not
+  // reproduced: the x extent is closed to the periodic edges.  The rim
+  // clipping in y stays GDAL's.
+  if (t.reproject && !t.gl && t.src.kind == GSKYHIP_CRS_GEOS &&
+      (t.dst.kind == GSKYHIP_CRS_WEBMERC || t.dst.kind == GSKYHIP_CRS_LONGLAT) && t.dst_gt[2] == 0.0 &&
+      t.dst_gt[4] == 0.0) {
+    if (geos_seam<NT>(t, nInX, nInY) && err == 0) {
+      const bool ll = t.dst.kind == GSKYHIP_CRS_LONGLAT;
+      const double half = ll ? 180.0 : kPi * t.dst.a * t.dst.k0, mid = ll ? 0.0 : t.dst.x0;
+      const double pl = t.dst_igt[0] + (mid - half) * t.dst_igt[1], pr = t.dst_igt[0] + (mid + half) * t.dst_igt[1];
+      ext[0] = fmin(ext[0], fmin(pl, pr));
+      ext[2] = fmax(ext[2], fmax(pl, pr));
+    }
+  }
   if (lane != 0) return;
 
   // ---- overview pick (warp.go:156-198)

@@ -113,8 +113,10 @@ def encode_netcdf(bands: Sequence[torch.Tensor], geot: Sequence[float], epsg: in
 
 def encode_netcdf_host(bands: Sequence[np.ndarray], geot: Sequence[float], epsg: int,
                        nodata: Optional[Sequence[float]] = None, names: Optional[Sequence[str]] = None,
-                       zlevel: int = 6, uint16: bool = False, threads: int = 4) -> bytes:
-    """encode_netcdf of host numpy bands (gskyhip_encode_netcdf_host; no device)."""
+                       zlevel: int = 6, uint16: bool = False, threads: int = 4, srs: Optional[str] = None) -> bytes:
+    """encode_netcdf of host numpy bands (gskyhip_encode_netcdf_host; no device).
+    `srs` (a PROJ string or WKT) replaces `epsg` for an SRS without a code
+    (the geostationary family)."""
     codes = {np.dtype(np.uint8): 1, np.dtype(np.int8): 100, np.dtype(np.int16): 3, np.dtype(np.float32): 6,
              np.dtype(np.uint16): 2}
     if not bands:
@@ -134,6 +136,12 @@ def encode_netcdf_host(bands: Sequence[np.ndarray], geot: Sequence[float], epsg:
     gt = (C.c_double * 6)(*[float(v) for v in geot])
     nd = np.asarray(nodata, np.float64) if nodata is not None else None
     nm = (C.c_char_p * n)(*[s.encode() for s in names]) if names is not None else None
+    if srs:
+        check(L.gskyhip_encode_netcdf_srs_host(ptrs, n, code, w, h, gt, srs.encode(),
+                                               nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm,
+                                               int(zlevel), int(threads), out.ctypes.data_as(C.c_void_p), cap,
+                                               C.byref(size)), "encode_netcdf_host")
+        return out[:size.value].tobytes()
     check(L.gskyhip_encode_netcdf_host(ptrs, n, code, w, h, gt, int(epsg),
                                        nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm, int(zlevel),
                                        int(threads), out.ctypes.data_as(C.c_void_p), cap, C.byref(size)),

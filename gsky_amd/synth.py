@@ -164,7 +164,21 @@ def _footprint_merc(g: SynthGranule, n=16):
         lon = np.clip(lon, -180, 180)
     else:   # any other SRS the library parses (UTM / MGA zones): its host transform
         from .tiles import crs_transform
-        lon, lat, _ = crs_transform(g.srs, "EPSG:4326", X, Y)
+        lon, lat, ok = crs_transform(g.srs, "EPSG:4326", X, Y)
+        if not ok.all():
+            # some edge points have no longitude / latitude (a geostationary
+            # granule's corners are space): sample the interior as well and
+            # keep the points that transform -- never a nan into a bbox
+            u, v = np.meshgrid(np.linspace(0.0, w, 41), np.linspace(0.0, h, 41))
+            Xi = gt[0] + u.ravel() * gt[1] + v.ravel() * gt[2]
+            Yi = gt[3] + u.ravel() * gt[4] + v.ravel() * gt[5]
+            lon2, lat2, ok2 = crs_transform(g.srs, "EPSG:4326", Xi, Yi)
+            lon, lat = np.concatenate([lon[ok], lon2[ok2]]), np.concatenate([lat[ok], lat2[ok2]])
+            if lon.size == 0:   # nothing of the granule is on the Earth: it meets no request
+                return np.inf, np.inf, -np.inf, -np.inf
+            if lon.max() - lon.min() > 180.0:   # the footprint crosses the antimeridian: every longitude
+                lon = np.array([-180.0, 180.0] * (lat.size // 2 + 1))[:lat.size]
+            lat = np.clip(lat, -85.05, 85.05)
     mx, my = merc_fwd(lon, lat)
     return mx.min(), my.min(), mx.max(), my.max()
 
@@ -338,6 +352,42 @@ def config_polar(scale: float = 1.0, tiles_per_side: int = 16, tile_px: int = 25
     cfg = config_utm(scale, tiles_per_side, tile_px, grid, srs=srs, origin=origin)
     cfg.name = "STERE"
     return cfg
+
+
+GEOS_SRS = "+proj=geos +lon_0=140.7 +h=35785863 +a=6378137 +b=6356752.3 +sweep=y"
+
+
+def config_geos(n: int = 1100, res: float = 10000.0, origins=None, tiles=None, tiles_per_side: int = 2,
+                tile_px: int = 256, srs: str = GEOS_SRS) -> SynthConfig:
+    """Himawari-like geostationary granules (140.7 E, +sweep=y, north-up):
+    int16 granules of n x n pixels of `res` metres on the square full-disc
+    grid centred on the sub-satellite point.  `origins`: the top-left corner
+    (x, y) of each granule in projected metres (default: one granule centred
+    on the sub-satellite point -- at 1100 x 10 km the whole disc, its corners
+    and rim in space).  `tiles`: the EPSG:3857 requests (bbox, w, h); default
+    tiles_per_side^2 tiles of tile_px over the part of the granules that is on
+    the Earth.  Nearest, the C2 scale and palette."""
+    if origins is None:
+        origins = [(-0.5 * n * res, 0.5 * n * res)]
+    def make(k):
+        x0, y0 = origins[k]
+        idx = np.arange(n * n, dtype=np.uint64).reshape(n, n) + np.uint64((SEED0 + 0x6E05 + k) << 32)
+        v = (splitmix64(idx) % np.uint64(10000)).astype(np.int16)
+        v[uniform01(splitmix64(idx)) < 0.02] = -999
+        x1, y1 = x0 + n * res, y0 - n * res
+        poly = "POLYGON ((%.1f %.1f,%.1f %.1f,%.1f %.1f,%.1f %.1f,%.1f %.1f))" % (x0, y0, x1, y0, x1, y1, x0, y1, x0, y0)
+        return SynthGranule(v, [float(x0), float(res), 0.0, float(y0), 0.0, -float(res)], srs, -999.0,
+                            1577836800.0 + 600.0 * k, poly)
+
+    granules = [make(k) for k in range(len(origins))]
+    if tiles is None:
+        fps = np.array([_footprint_merc(g) for g in granules])
+        fps = fps[np.isfinite(fps).all(axis=1)]
+        bbox = (float(np.floor(fps[:, 0].min())), float(np.floor(fps[:, 1].min())), float(np.ceil(fps[:, 2].max())),
+                float(np.ceil(fps[:, 3].max())))
+        tiles = _grid_tiles(bbox, tiles_per_side, tiles_per_side, tile_px)
+    pairs = _index_pairs(granules, tiles)
+    return SynthConfig("GEOS", granules, "EPSG:3857", list(tiles), pairs, [""], (0.0, 0.0, 10000.0, 0), PALETTE_GSKY)
 
 
 def subset(cfg: SynthConfig, tile_ids) -> SynthConfig:

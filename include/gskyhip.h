@@ -66,6 +66,18 @@ extern "C" {
                                     * / 3413 / 3976, UPS 32661 / 32761,          *
                                     * +proj=stere +lat_0=+-90 / +proj=ups; akm1  *
                                     * in c, |lat_ts| in phi1                     */
+#define GSKYHIP_CRS_GEOS 7         /* geostationary satellite view, ellipsoid or *
+                                    * sphere: +proj=geos +h +lon_0 +sweep (y:    *
+                                    * Himawari / Meteosat, x: GOES-R), WKT1       *
+                                    * Geostationary_Satellite, CF geostationary; *
+                                    * no EPSG code.  In units of a: h / a in     *
+                                    * phi1, sweep flag (1: x) in phi2, radius_g  *
+                                    * = 1 + h / a in n, radius_g^2 - 1 in c,     *
+                                    * radius_p = sqrt(1 - es) in dd, 1 - es in   *
+                                    * rho0, 1 / (1 - es) in ec.  The first kind  *
+                                    * whose transform fails over whole regions:  *
+                                    * forward beyond the limb, inverse off the   *
+                                    * disc (ok = 0 in gskyhip_crs_transform)     */
 
 typedef struct {
     int32_t kind;
@@ -510,6 +522,15 @@ int gskyhip_encode_netcdf(const void *const *bands, int n_bands, int dtype, int 
 int gskyhip_encode_netcdf_host(const void *const *bands, int n_bands, int dtype, int width, int height,
                                const double *geot, int epsg, const double *nodata, const char *const *names,
                                int zlevel, int n_threads, uint8_t *out, int64_t capacity, int64_t *size);
+/* The same for an SRS given as gskyhip_crs_from_srs takes it, for the
+ * families without an EPSG code (geostationary: the CF `geostationary`
+ * mapping with sweep_angle_axis always written, and the WKT1
+ * Geostationary_Satellite node as spatial_ref).  GSKYHIP_E_CRS for an SRS
+ * outside the supported families. */
+int gskyhip_encode_netcdf_srs_host(const void *const *bands, int n_bands, int dtype, int width, int height,
+                                   const double *geot, const char *srs, const double *nodata,
+                                   const char *const *names, int zlevel, int n_threads, uint8_t *out,
+                                   int64_t capacity, int64_t *size);
 
 /* ---- drill (WPS zonal statistics) --------------------------------------- */
 /* readData (worker/gdalprocess/drill.go:90-227), mean / pixel-count mode,
