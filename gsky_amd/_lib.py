@@ -25,6 +25,9 @@ RESAMPLE_NEAREST, RESAMPLE_BILINEAR = 0, 1
 # value-type hint bits of gskyhip_render_tiles_typed
 VT_BIT = {BYTE: 1, SIGNEDBYTE: 2, INT16: 4, UINT16: 8, FLOAT32: 16}
 MAX_OVR = 12
+# overview pyramid methods of gskyhip_build_overviews
+OVR_NEAREST, OVR_AVERAGE = 0, 1
+OVR_METHODS = {"nearest": OVR_NEAREST, "average": OVR_AVERAGE}
 MAX_BIT_TESTS = 8
 
 ERRORS = {0: "OK", -1: "bad argument", -2: "raster type not implemented", -3: "HIP runtime error",
@@ -106,6 +109,8 @@ EXPORTS = [
     "gskyhip_netcdf_bound", "gskyhip_encode_netcdf", "gskyhip_encode_netcdf_host", "gskyhip_encode_netcdf_srs_host",
     "gskyhip_geotiff_info", "gskyhip_geotiff_read_host", "gskyhip_geotiff_read", "gskyhip_register_geotiff",
     "gskyhip_netcdf_info", "gskyhip_netcdf_srs", "gskyhip_netcdf_read_host", "gskyhip_netcdf_read", "gskyhip_register_netcdf",
+    "gskyhip_overview_levels", "gskyhip_build_overviews", "gskyhip_register_geotiff_ovr", "gskyhip_register_netcdf_ovr",
+    "gskyhip_service_register_granule_ovr",
 ]
 
 _lib = None
@@ -135,6 +140,13 @@ def lib() -> C.CDLL:
     L.gskyhip_netcdf_read_host.argtypes = [C.c_char_p, ci, vp, i64]
     L.gskyhip_netcdf_read.argtypes = [C.c_char_p, ci, vp, i64, vp]
     L.gskyhip_register_netcdf.argtypes = [C.c_char_p, ci]
+    if hasattr(L, "gskyhip_build_overviews"):   # absent from kept earlier builds (GSKYHIP_LIB=<name>)
+        L.gskyhip_overview_levels.argtypes = [ci, ci, ci, vp, vp]
+        L.gskyhip_build_overviews.argtypes = [vp, ci, ci, ci, ci, ci, d, ci, ci, vp, vp, vp, vp]
+        L.gskyhip_register_geotiff_ovr.argtypes = [C.c_char_p, ci, ci, ci]
+        L.gskyhip_register_netcdf_ovr.argtypes = [C.c_char_p, ci, ci, ci]
+        L.gskyhip_service_register_granule_ovr.argtypes = [C.c_char_p, C.c_char_p, ci, C.POINTER(Granule), vp,
+                                                           C.c_char_p, ci, ci]
     L.warp_operation_fast.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(d), vp, C.c_char_p, C.POINTER(d),
                                       ci, ci, ci, ci, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci),
                                       C.POINTER(d), C.POINTER(ci), C.POINTER(ci)]
@@ -225,6 +237,14 @@ def lib() -> C.CDLL:
     L.gskyhip_version.restype = C.c_char_p
     _lib = L
     return L
+
+
+def ovr_method(name: str) -> int:
+    """GSKYHIP_OVR_* of "nearest" / "average" (ValueError otherwise)."""
+    try:
+        return OVR_METHODS[name]
+    except (KeyError, TypeError):
+        raise ValueError("overview method must be 'nearest' or 'average', not %r" % (name,)) from None
 
 
 def check(code: int, what: str = "") -> None:

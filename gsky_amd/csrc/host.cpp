@@ -645,6 +645,9 @@ struct DropIn {
   std::mutex mu;
   std::map<std::pair<std::string, int>, RegPtr> reg;
   uint64_t tick = 0;     // one per warp batch (LRU order of the ingest cache)
+  // (path, band) ingested by the _ovr calls -> (method, min_size): a re-read of the
+  // file (changed on disk, or evicted and requested again) builds the same pyramid
+  std::map<std::pair<std::string, int>, std::pair<int, int>> ovr_asked;
   std::map<std::string, std::shared_ptr<struct GeoLocEntry>> geolocs;   // by GeoLocOpts (geoloc_entry)
 };
 DropIn &dropin() {
@@ -709,11 +712,57 @@ bool have_gpu() {
   return hipGetDeviceCount(&n) == hipSuccess && n > 0;
 }
 
+// The pyramid an ingest builds for a band that came without overviews
+// (overview.hip): method GSKYHIP_OVR_* or -1 (none), min_size as
+// gskyhip_overview_levels takes it.  strict: a band type the pyramid does
+// not cover fails the ingest (the _ovr calls); else it is ingested without.
+struct OvrBuild {
+  int method = -1, min_size = 0;
+  bool strict = false;
+};
+
+bool ovr_type_ok(int dtype) {
+  return dtype == GSKYHIP_BYTE || dtype == GSKYHIP_INT16 || dtype == GSKYHIP_UINT16 || dtype == GSKYHIP_FLOAT32;
+}
+
+// Level sizes of the pyramid `ob` asks for into info (n_ovr 0 on entry), or
+// GSKYHIP_E_TYPE; *bytes grows by the levels' size.
+int ovr_plan(const OvrBuild &ob, gskyhip_raster_info &info, int64_t *bytes) {
+  if (ob.method < 0 || info.n_ovr > 0) return 0;   // a file's own overviews always win
+  if (ob.method != GSKYHIP_OVR_NEAREST && ob.method != GSKYHIP_OVR_AVERAGE) return GSKYHIP_E_ARG;
+  if (!ovr_type_ok(info.dtype)) return ob.strict ? GSKYHIP_E_TYPE : 0;
+  const int n = gskyhip_overview_levels(info.xsize, info.ysize, ob.min_size, info.ovr_xsize, info.ovr_ysize);
+  if (n < 0) return n;
+  info.n_ovr = n;
+  for (int k = 0; k < n; k++) *bytes += (int64_t)info.ovr_xsize[k] * info.ovr_ysize[k] * type_size(info.dtype);
+  return 0;
+}
+
+// Allocate (into r.owned, after level 0) and build the levels ovr_plan sized;
+// returns once they are complete, so any stream may read them.
+int ovr_build(const gskyhip_raster_info &info, int method, Registered &r) {
+  if (info.n_ovr <= 0) return 0;   // nothing planned (a small band, or a type ingested without)
+  void *lv[GSKYHIP_MAX_OVR];
+  const int ts = type_size(info.dtype);
+  for (int k = 0; k < info.n_ovr; k++) {
+    void *p = nullptr;
+    if (hipMalloc(&p, (size_t)((int64_t)info.ovr_xsize[k] * info.ovr_ysize[k] * ts)) != hipSuccess) return GSKYHIP_E_HIP;
+    r.owned.push_back(p);
+    lv[k] = p;
+  }
+  const int rc = gskyhip_build_overviews(r.owned[0], info.dtype, info.signed_byte, info.xsize, info.ysize,
+                                         info.has_nodata, info.nodata, method, info.n_ovr, lv, info.ovr_xsize,
+                                         info.ovr_ysize, nullptr);
+  if (rc) return rc;
+  return hipStreamSynchronize(nullptr) == hipSuccess ? 0 : GSKYHIP_E_HIP;
+}
+
 // GDALOpenEx + GDALGetRasterBand of a GeoTIFF (warp.go:89-118) for the
 // registry: every level of band `band` decoded into HBM the library owns
-// (ingest.hip), registered under (path, band) with the file's SRS.  Returns
+// (ingest.hip), registered under (path, band) with the file's SRS; a
+// band without overviews gets the pyramid `ob` asks for.  Returns
 // 0, 1 (open failed), 2 (no such band) or GSKYHIP_E_*.  d.mu held.
-int ingest_geotiff_locked(DropIn &d, const std::string &path, int band) {
+int ingest_geotiff_locked(DropIn &d, const std::string &path, int band, const OvrBuild &ob) {
   gskyhip_raster_info info;
   int rc = gskyhip_geotiff_info(path.c_str(), &info);
   if (rc) return rc;
@@ -726,6 +775,8 @@ int ingest_geotiff_locked(DropIn &d, const std::string &path, int band) {
   int64_t total = 0;
   for (int lv = 0; lv <= info.n_ovr; lv++)
     total += (int64_t)(lv ? info.ovr_xsize[lv - 1] : info.xsize) * (lv ? info.ovr_ysize[lv - 1] : info.ysize) * ts;
+  const bool build = ob.method >= 0 && info.n_ovr == 0;
+  if (build && (rc = ovr_plan(ob, info, &total))) return rc;
   d.reg.erase({path, band});   // a batch still holding the old entry keeps it alive
   evict_for(d, total);
   r.bytes = total;
@@ -738,7 +789,9 @@ int ingest_geotiff_locked(DropIn &d, const std::string &path, int band) {
     if (hipMalloc(&p, (size_t)(xs * ys * ts)) != hipSuccess) return GSKYHIP_E_HIP;
     r.owned.push_back(p);
     if ((rc = gskyhip_geotiff_read(path.c_str(), band, lv, p, xs * ys * ts, nullptr))) return rc;
+    if (build) break;   // the planned levels are built, not read
   }
+  if (build && (rc = ovr_build(info, ob.method, r))) return rc;
   gskyhip_granule &g = r.g;
   g.data = r.owned[0];
   g.dtype = info.dtype; g.xsize = info.xsize; g.ysize = info.ysize; g.signed_byte = info.signed_byte;
@@ -760,7 +813,7 @@ int ingest_geotiff_locked(DropIn &d, const std::string &path, int band) {
 
 // The same for a netCDF classic variable band (band_query semantics,
 // warp.go:89-101: the band is registered under (path, band)).
-int ingest_netcdf_locked(DropIn &d, const std::string &path, int band) {
+int ingest_netcdf_locked(DropIn &d, const std::string &path, int band, const OvrBuild &ob) {
   gskyhip_raster_info info;
   std::string srs_no, srs_cf;
   int rc = netcdf_info_srs(path.c_str(), &info, &srs_no, &srs_cf);
@@ -772,21 +825,28 @@ int ingest_netcdf_locked(DropIn &d, const std::string &path, int band) {
   RegPtr rp = std::make_shared<Registered>();
   Registered &r = *rp;
   void *p = nullptr;
-  const int64_t bytes = (int64_t)info.xsize * info.ysize * ts;
+  const int64_t bytes0 = (int64_t)info.xsize * info.ysize * ts;
+  int64_t bytes = bytes0;
+  if ((rc = ovr_plan(ob, info, &bytes))) return rc;
   d.reg.erase({path, band});   // a batch still holding the old entry keeps it alive
   evict_for(d, bytes);
   r.bytes = bytes;
   r.last_use = d.tick;
   r.stamped = file_stamp(path, r.mtime_ns, r.fsize);
   if (!r.stamped) r.fsize = 0;
-  if (hipMalloc(&p, (size_t)bytes) != hipSuccess) return GSKYHIP_E_HIP;
+  if (hipMalloc(&p, (size_t)bytes0) != hipSuccess) return GSKYHIP_E_HIP;
   r.owned.push_back(p);
-  if ((rc = gskyhip_netcdf_read(path.c_str(), band, p, bytes, nullptr))) return rc;
+  if ((rc = gskyhip_netcdf_read(path.c_str(), band, p, bytes0, nullptr))) return rc;
+  if ((rc = ovr_build(info, ob.method, r))) return rc;
   gskyhip_granule &g = r.g;
   g.data = p;
   g.dtype = info.dtype; g.xsize = info.xsize; g.ysize = info.ysize; g.signed_byte = info.signed_byte;
   for (int k = 0; k < 6; k++) g.geot[k] = info.geot[k];
   g.nodata = info.nodata; g.has_nodata = info.has_nodata;
+  g.n_ovr = info.n_ovr;
+  for (int k = 0; k < info.n_ovr; k++) {
+    g.ovr_data[k] = r.owned[k + 1]; g.ovr_xsize[k] = info.ovr_xsize[k]; g.ovr_ysize[k] = info.ovr_ysize[k];
+  }
   g.block_x = info.block_x; g.block_y = info.block_y;
   // "" -> no SRS (the warp takes WGS84, warp.go:107-112); "?" or one the
   // warp cannot parse -> the request fails with GSKYHIP_E_CRS
@@ -824,8 +884,25 @@ struct GeoLocEntry {
 };
 using GeoLocPtr = std::shared_ptr<GeoLocEntry>;
 
-int ingest_geotiff_locked(DropIn &d, const std::string &path, int band);
-int ingest_netcdf_locked(DropIn &d, const std::string &path, int band);
+int ingest_geotiff_locked(DropIn &d, const std::string &path, int band, const OvrBuild &ob);
+int ingest_netcdf_locked(DropIn &d, const std::string &path, int band, const OvrBuild &ob);
+
+// The pyramid of the drop-in's own ingest (an unregistered path handed to
+// warp_operation_fast, here or in the daemon): GSKYHIP_BUILD_OVERVIEWS =
+// nearest | average, GSKYHIP_OVERVIEW_MIN_SIZE optional; read once.  Unset,
+// empty or anything else: none.
+const OvrBuild &auto_ovr() {
+  static const OvrBuild ob = [] {
+    OvrBuild o;
+    const char *m = std::getenv("GSKYHIP_BUILD_OVERVIEWS");
+    if (m && !std::strcmp(m, "nearest")) o.method = GSKYHIP_OVR_NEAREST;
+    else if (m && !std::strcmp(m, "average")) o.method = GSKYHIP_OVR_AVERAGE;
+    const char *ms = std::getenv("GSKYHIP_OVERVIEW_MIN_SIZE");
+    if (ms) o.min_size = std::atoi(ms);
+    return o;
+  }();
+  return ob;
+}
 bool is_geotiff_path(const std::string &p);
 
 bool is_netcdf_path(const std::string &p) {
@@ -849,7 +926,13 @@ RegPtr lookup_dataset(DropIn &d, const std::string &path, int band, int *irc) {
   }
   const bool nc = is_netcdf_path(path);
   if (it == d.reg.end() && (nc || is_geotiff_path(path))) {
-    *irc = nc ? ingest_netcdf_locked(d, path, band) : ingest_geotiff_locked(d, path, band);
+    OvrBuild ob = auto_ovr();
+    const auto asked = d.ovr_asked.find({path, band});
+    if (asked != d.ovr_asked.end()) {
+      ob.method = asked->second.first;
+      ob.min_size = asked->second.second;
+    }
+    *irc = nc ? ingest_netcdf_locked(d, path, band, ob) : ingest_geotiff_locked(d, path, band, ob);
     if (*irc == 0) it = d.reg.find({path, band});
   }
   if (it == d.reg.end()) return RegPtr();
@@ -1107,6 +1190,7 @@ int gskyhip_unregister_all(void) {
   DropIn &d = dropin();
   std::lock_guard<std::mutex> lk(d.mu);
   d.reg.clear();       // HBM of ingested granules is freed once no batch in flight holds it
+  d.ovr_asked.clear();
   d.geolocs.clear();
   return 0;
 }
@@ -1115,14 +1199,38 @@ int gskyhip_register_geotiff(const char *path, int band) {
   if (!path) return GSKYHIP_E_ARG;
   DropIn &d = dropin();
   std::lock_guard<std::mutex> lk(d.mu);
-  return ingest_geotiff_locked(d, path, band);
+  d.ovr_asked.erase({path, band});
+  return ingest_geotiff_locked(d, path, band, OvrBuild());
 }
 
 int gskyhip_register_netcdf(const char *path, int band) {
   if (!path) return GSKYHIP_E_ARG;
   DropIn &d = dropin();
   std::lock_guard<std::mutex> lk(d.mu);
-  return ingest_netcdf_locked(d, path, band);
+  d.ovr_asked.erase({path, band});
+  return ingest_netcdf_locked(d, path, band, OvrBuild());
+}
+
+int gskyhip_register_geotiff_ovr(const char *path, int band, int method, int min_size) {
+  if (!path || (method != GSKYHIP_OVR_NEAREST && method != GSKYHIP_OVR_AVERAGE)) return GSKYHIP_E_ARG;
+  DropIn &d = dropin();
+  std::lock_guard<std::mutex> lk(d.mu);
+  OvrBuild ob;
+  ob.method = method; ob.min_size = min_size; ob.strict = true;
+  const int rc = ingest_geotiff_locked(d, path, band, ob);
+  if (rc == 0) d.ovr_asked[{path, band}] = {method, min_size};
+  return rc;
+}
+
+int gskyhip_register_netcdf_ovr(const char *path, int band, int method, int min_size) {
+  if (!path || (method != GSKYHIP_OVR_NEAREST && method != GSKYHIP_OVR_AVERAGE)) return GSKYHIP_E_ARG;
+  DropIn &d = dropin();
+  std::lock_guard<std::mutex> lk(d.mu);
+  OvrBuild ob;
+  ob.method = method; ob.min_size = min_size; ob.strict = true;
+  const int rc = ingest_netcdf_locked(d, path, band, ob);
+  if (rc == 0) d.ovr_asked[{path, band}] = {method, min_size};
+  return rc;
 }
 
 }  // extern "C"

@@ -2345,7 +2345,8 @@ int launch_pair_touched(void *workspace, int n_tiles, int n_pairs, int max_h, in
   }
   if (segs.empty()) return 0;
   const int64_t ew_words = ebits / 32, lw_words = lbits / 32;
-  const size_t bytes = (size_t)(ew_words + lw_words) * 4 + base.size() * 8 + (ew.size() + lw.size()) * 8 + 16;
+  // (+ 8: the word that aligns dbase when the two maps hold an odd number of words)
+  const size_t bytes = (size_t)(ew_words + lw_words) * 4 + 8 + base.size() * 8 + (ew.size() + lw.size()) * 8 + 16;
   char *dev = nullptr;
   if (hipMalloc((void **)&dev, bytes) != hipSuccess) return GSKYHIP_E_HIP;
   uint32_t *eb = (uint32_t *)dev, *lb = eb + ew_words;

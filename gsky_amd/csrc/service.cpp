@@ -130,7 +130,7 @@ bool send_msg(int fd, uint32_t op, const std::vector<char> &payload) {
 // nothing -- so one bad header cannot make the daemon allocate gigabytes.
 uint64_t max_payload(uint32_t op) {
   switch (op) {
-    case SVC_REGISTER: return 1ull << 36;
+    case SVC_REGISTER: case SVC_REGISTER_OVR: return 1ull << 36;
     case SVC_WARP: case SVC_WARP_SHM: return 1ull << 20;
     default: return 64;
   }
@@ -458,7 +458,9 @@ void complete_loop(Service *s) {
 // SVC_REGISTER payload: path, band, srs, granule header (host struct; data
 // pointers ignored), level-0 bytes, n_ovr x overview bytes.  Waits until no
 // batch is in flight (and holds new ones back) while it changes the registry.
-int do_register(Service *s, In &in) {
+// SVC_REGISTER_OVR (build_ovr): no overview bytes; int32 method, min_size
+// follow level 0, and the daemon builds the pyramid in its own HBM.
+int do_register(Service *s, In &in, bool build_ovr) {
   const std::string path = in.get_str();
   const int32_t band = in.get<int32_t>();
   const std::string srs = in.get_str();
@@ -503,7 +505,25 @@ int do_register(Service *s, In &in) {
   int e = upload(p, n, &dev);
   if (e) return fail(e);
   g.data = dev;
-  for (int k = 0; k < g.n_ovr; k++) {
+  if (build_ovr) {
+    const int32_t method = in.get<int32_t>(), min_size = in.get<int32_t>();
+    if (!in.ok || g.n_ovr != 0) return fail(GSKYHIP_E_ARG);
+    const int nl = gskyhip_overview_levels(g.xsize, g.ysize, min_size, g.ovr_xsize, g.ovr_ysize);
+    if (nl < 0) return fail(nl);
+    void *lv[GSKYHIP_MAX_OVR];
+    for (int k = 0; k < nl; k++) {
+      if (hipMalloc(&lv[k], (size_t)g.ovr_xsize[k] * (size_t)g.ovr_ysize[k] * (size_t)type_size(g.dtype)) != hipSuccess)
+        return fail(GSKYHIP_E_HIP);
+      mine.push_back(lv[k]);
+      g.ovr_data[k] = lv[k];
+    }
+    if ((e = gskyhip_build_overviews(dev, g.dtype, g.signed_byte, g.xsize, g.ysize, g.has_nodata, g.nodata, method, nl,
+                                     lv, g.ovr_xsize, g.ovr_ysize, nullptr)))
+      return fail(e);
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(GSKYHIP_E_HIP);   // complete before any batch reads it
+    g.n_ovr = nl;
+  }
+  for (int k = 0; !build_ovr && k < g.n_ovr; k++) {
     const char *po = in.get_bytes(n);
     if (!in.ok || n != (uint64_t)g.ovr_xsize[k] * (uint64_t)g.ovr_ysize[k] * (uint64_t)type_size(g.dtype))
       return fail(GSKYHIP_E_ARG);
@@ -673,7 +693,9 @@ void conn_serve(Service *s, int fd) {
       if (!sent) break;   // the worker died (SIGKILL): drop the reply
       continue;
     } else if (op == SVC_REGISTER) {
-      o.put<int32_t>(do_register(s, in));
+      o.put<int32_t>(do_register(s, in, false));
+    } else if (op == SVC_REGISTER_OVR) {
+      o.put<int32_t>(do_register(s, in, true));
     } else if (op == SVC_UNREGISTER_ALL) {
       o.put<int32_t>(do_unregister_all(s));
     } else if (op == SVC_STATS) {
@@ -1017,6 +1039,30 @@ int gskyhip_service_register_granule(const char *socket_path, const char *path, 
   for (int k = 0; k < g->n_ovr; k++) o.put_bytes(ovr_data[k], (size_t)g->ovr_xsize[k] * g->ovr_ysize[k] * ts);
   std::vector<char> rep;
   if (!exchange(socket_path, SVC_REGISTER, o.b, rep) || rep.size() < 4) return GSKYHIP_E_SERVICE;
+  int32_t rc;
+  std::memcpy(&rc, rep.data(), 4);
+  return rc;
+}
+
+int gskyhip_service_register_granule_ovr(const char *socket_path, const char *path, int band,
+                                         const gskyhip_granule *g, const void *data, const char *srs, int method,
+                                         int min_size) {
+  if (!socket_path || !path || !g || !data) return GSKYHIP_E_ARG;
+  if (method != GSKYHIP_OVR_NEAREST && method != GSKYHIP_OVR_AVERAGE) return GSKYHIP_E_ARG;
+  const int ts = type_size(g->dtype);
+  if (ts <= 0 || ts == 8 || g->dtype == GSKYHIP_UINT32 || g->dtype == GSKYHIP_INT32) return GSKYHIP_E_TYPE;
+  gskyhip_granule h = *g;
+  h.n_ovr = 0;
+  Out o;
+  o.put_str(path);
+  o.put<int32_t>(band);
+  o.put_str(srs ? srs : "");
+  o.put(h);
+  o.put_bytes(data, (size_t)h.xsize * h.ysize * ts);
+  o.put<int32_t>(method);
+  o.put<int32_t>(min_size);
+  std::vector<char> rep;
+  if (!exchange(socket_path, SVC_REGISTER_OVR, o.b, rep) || rep.size() < 4) return GSKYHIP_E_SERVICE;
   int32_t rc;
   std::memcpy(&rc, rep.data(), 4);
   return rc;

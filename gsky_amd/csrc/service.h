@@ -27,7 +27,8 @@ constexpr uint32_t kSvcMagic = 0x594B5347u;   // "GSKY"
 // (a sealed memfd passed with SCM_RIGHTS on the first request of a
 // connection, or when it grows); SVC_WARP carries the window in the socket.
 enum SvcOp : uint32_t {
-  SVC_WARP = 1, SVC_REGISTER = 2, SVC_UNREGISTER_ALL = 3, SVC_STATS = 4, SVC_SHUTDOWN = 5, SVC_WARP_SHM = 6
+  SVC_WARP = 1, SVC_REGISTER = 2, SVC_UNREGISTER_ALL = 3, SVC_STATS = 4, SVC_SHUTDOWN = 5, SVC_WARP_SHM = 6,
+  SVC_REGISTER_OVR = 7   // SVC_REGISTER without overviews + method, min_size: the daemon builds the pyramid
 };
 
 // Forward one request to the service at `sock`; 0, or GSKYHIP_E_SERVICE when

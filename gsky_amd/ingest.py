@@ -12,7 +12,8 @@ from typing import List, Optional, Tuple
 
 import numpy as np
 
-from ._lib import BYTE, FLOAT32, FLOAT64, INT16, INT32, UINT16, UINT32, GskyError, RasterInfo, lib
+from ._lib import (BYTE, FLOAT32, FLOAT64, INT16, INT32, MAX_OVR, UINT16, UINT32, GskyError, RasterInfo, lib,
+                   ovr_method)
 
 NP_DTYPE = {BYTE: np.uint8, UINT16: np.uint16, INT16: np.int16, UINT32: np.uint32, INT32: np.int32,
             FLOAT32: np.float32, FLOAT64: np.float64}
@@ -108,10 +109,59 @@ def read(path: str, band: int = 1, level: int = 0, device=None):
     return out
 
 
-def register(path: str, band: int = 1) -> None:
+def overview_levels(xsize: int, ysize: int, min_size: int = 256) -> List[Tuple[int, int]]:
+    """(xsize, ysize) of the pyramid levels gskyhip_build_overviews makes,
+    finest first: ceil(n / 2^k) per axis while the level before is larger
+    than min_size (<= 0: 256), at most 12."""
+    xs = (C.c_int32 * MAX_OVR)()
+    ys = (C.c_int32 * MAX_OVR)()
+    n = lib().gskyhip_overview_levels(int(xsize), int(ysize), int(min_size), xs, ys)
+    if n < 0:
+        raise GskyError(n, "overview_levels")
+    return [(xs[k], ys[k]) for k in range(n)]
+
+
+def build_overviews(tensor, nodata: Optional[float] = None, method: str = "nearest", min_size: int = 256,
+                    signed_byte: bool = False) -> list:
+    """The overview pyramid of a 2-D HBM tensor (uint8, int8, int16, uint16
+    or float32), built by the overview kernel on the current stream: a list
+    of new tensors, finest first (include/gskyhip.h for the rules)."""
+    import torch
+    from .tiles import DTYPE_OF_TORCH
+    m = ovr_method(method)
+    if tensor.dim() != 2 or not tensor.is_cuda:
+        raise ValueError("build_overviews takes a 2-D tensor in HBM")
+    if tensor.dtype not in DTYPE_OF_TORCH:
+        raise GskyError(-2, "build_overviews (%s)" % tensor.dtype)
+    t = tensor.contiguous()
+    ysize, xsize = t.shape
+    sizes = overview_levels(xsize, ysize, min_size)
+    out = [torch.empty((h, w), dtype=t.dtype, device=t.device) for w, h in sizes]
+    n = len(out)
+    ptrs = (C.c_void_p * max(1, n))(*[o.data_ptr() for o in out])
+    xs = (C.c_int32 * max(1, n))(*[w for w, _ in sizes])
+    ys = (C.c_int32 * max(1, n))(*[h for _, h in sizes])
+    with torch.cuda.device(t.device):
+        stream = torch.cuda.current_stream(t.device).cuda_stream
+        rc = lib().gskyhip_build_overviews(C.c_void_p(t.data_ptr()), DTYPE_OF_TORCH[t.dtype],
+                                           int(signed_byte or t.dtype == torch.int8), xsize, ysize,
+                                           int(nodata is not None), float(nodata if nodata is not None else -1e10),
+                                           m, n, ptrs, xs, ys, C.c_void_p(stream))
+    if rc:
+        raise GskyError(rc, "build_overviews")
+    return out
+
+
+def register(path: str, band: int = 1, overviews: Optional[str] = None, min_size: int = 256) -> None:
     """Decode every level of (path, band) into library-owned HBM and register
-    it for warp_operation_fast (worker.warp_raster)."""
-    fn = lib().gskyhip_register_netcdf if is_netcdf(path) else lib().gskyhip_register_geotiff
-    rc = fn(path.encode(), band)
+    it for warp_operation_fast (worker.warp_raster).  overviews = "nearest" /
+    "average": a band that comes without overviews gets a pyramid of that
+    method down to min_size, built on the GPU (a file's own overviews win)."""
+    if overviews is None:
+        fn = lib().gskyhip_register_netcdf if is_netcdf(path) else lib().gskyhip_register_geotiff
+        rc = fn(path.encode(), band)
+    else:
+        fn = lib().gskyhip_register_netcdf_ovr if is_netcdf(path) else lib().gskyhip_register_geotiff_ovr
+        rc = fn(path.encode(), band, ovr_method(overviews), int(min_size))
     if rc:
         raise GskyError(rc, "register (%s)" % path)

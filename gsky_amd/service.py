@@ -76,9 +76,15 @@ class WarpService:
 
     def register_granule(self, path: str, band: int, data: np.ndarray, geot: Sequence[float], srs: str = "",
                          nodata: Optional[float] = None, overviews: Sequence[np.ndarray] = (),
-                         signed_byte: bool = False, block=(0, 0)) -> None:
+                         signed_byte: bool = False, block=(0, 0), build_overviews: Optional[str] = None,
+                         min_size: int = 256) -> None:
         """Uploads a band (and its overviews) into the daemon's HBM under
-        (path, band): the daemon-side GDALOpenEx of warp.go:89-101."""
+        (path, band): the daemon-side GDALOpenEx of warp.go:89-101.
+        build_overviews = "nearest" / "average": no overviews are uploaded;
+        the daemon builds the pyramid in its HBM (down to min_size)."""
+        if build_overviews is not None and len(overviews):
+            raise ValueError("build_overviews and explicit overviews exclude each other")
+        method = _lib.ovr_method(build_overviews) if build_overviews is not None else None
         d = np.ascontiguousarray(data)
         ovr = [np.ascontiguousarray(o, dtype=d.dtype) for o in overviews]
         g = _lib.Granule()
@@ -93,6 +99,12 @@ class WarpService:
         for k, o in enumerate(ovr):
             g.ovr_ysize[k], g.ovr_xsize[k] = o.shape
         g.block_x, g.block_y = block
+        if method is not None:
+            check(lib().gskyhip_service_register_granule_ovr(self.socket_path.encode(), path.encode(), int(band),
+                                                             C.byref(g), C.c_void_p(d.ctypes.data),
+                                                             srs.encode() if srs else None, method, int(min_size)),
+                  "service register")
+            return
         optrs = (C.c_void_p * max(1, len(ovr)))(*[o.ctypes.data for o in ovr])
         check(lib().gskyhip_service_register_granule(self.socket_path.encode(), path.encode(), int(band),
                                                      C.byref(g), C.c_void_p(d.ctypes.data), optrs,

@@ -82,12 +82,21 @@ class GranuleSet:
 
     def add(self, data: torch.Tensor, geot: Sequence[float], srs: str, nodata: Optional[float] = None,
             overviews: Sequence[torch.Tensor] = (), timestamp: float = 0.0, polygon: str = "",
-            namespace: str = "", signed_byte: bool = False) -> int:
+            namespace: str = "", signed_byte: bool = False, build_overviews: Optional[str] = None,
+            min_size: int = 256) -> int:
+        """build_overviews = "nearest" / "average": the pyramid is built on
+        the GPU (ingest.build_overviews, down to min_size) on the current
+        stream instead of passed in as `overviews`."""
         if data.dim() != 2:
             raise ValueError("granule data must be 2-D (ysize, xsize)")
         if len(overviews) > _lib.MAX_OVR:
             raise ValueError("too many overviews")
+        if build_overviews is not None and len(overviews):
+            raise ValueError("build_overviews and explicit overviews exclude each other")
         d = data.to(self.device).contiguous()
+        if build_overviews is not None:
+            from .ingest import build_overviews as _build
+            overviews = _build(d, nodata, build_overviews, min_size, signed_byte)
         ovr = [o.to(self.device).contiguous() for o in overviews]
         self.items.append(GranuleInfo(d, ovr, list(geot), srs, nodata, float(timestamp), polygon, namespace,
                                       signed_byte or data.dtype == torch.int8))

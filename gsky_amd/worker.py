@@ -73,10 +73,18 @@ class Result:
 
 def register_granule(path: str, band: int, data: torch.Tensor, geot, srs: str = "",
                      nodata: Optional[float] = None, overviews=(), signed_byte: bool = False,
-                     block=(0, 0)) -> None:
+                     block=(0, 0), build_overviews: Optional[str] = None, min_size: int = 256) -> None:
     """Make an HBM-resident band visible to warp_operation_fast under (path, band).
-    `block` = GDALGetBlockSize of the band ((0, 0): xsize x 1), for bytesRead."""
+    `block` = GDALGetBlockSize of the band ((0, 0): xsize x 1), for bytesRead.
+    build_overviews = "nearest" / "average": the pyramid is built on the GPU
+    (ingest.build_overviews, down to min_size) instead of passed in."""
     d = data.contiguous()
+    if build_overviews is not None:
+        if len(overviews):
+            raise ValueError("build_overviews and explicit overviews exclude each other")
+        from .ingest import build_overviews as _build
+        overviews = _build(d, nodata, build_overviews, min_size, signed_byte)
+        torch.cuda.current_stream(d.device).synchronize()   # the warp runs on streams of its own
     ovr = [o.contiguous() for o in overviews]
     g = _lib.Granule()
     g.block_x, g.block_y = block

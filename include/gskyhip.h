@@ -211,6 +211,53 @@ int gskyhip_netcdf_read(const char *path, int band, void *dev_out, int64_t out_b
  * warp_operation_fast does itself for an unregistered netCDF path. */
 int gskyhip_register_netcdf(const char *path, int band);
 
+/* ---- overview pyramids built on the GPU ---------------------------------- */
+/* For granules that come without overviews (netCDF, plain GeoTIFF, bands
+ * registered from HBM), so that the overview pick of the warp (warp.go:
+ * 156-198) has levels to choose from; what gdaladdo does offline.
+ * Level k is ceil(n / 2^k) per axis (GDAL's (n + f - 1) / f); levels are
+ * produced while max(xsize, ysize) of the level before exceeds min_size
+ * (<= 0: 256), at most GSKYHIP_MAX_OVR.
+ * NEAREST: level k (i, j) = level k-1 (2i, 2j) (QA / bit-mask bands).
+ * AVERAGE, cascaded: level k (i, j) = mean of the valid pixels among level
+ * k-1 (2i..2i+1, 2j..2j+1) clipped to the extent, from the stored (rounded)
+ * values of level k-1.  Invalid: has_nodata and equal to the typed nodata
+ * (GDALCopyWords of `nodata`, the warp's window fill, warp.go:247), or a
+ * float32 NaN.  No valid pixel: the typed nodata, or without a nodata value
+ * (an all-NaN float box) the quiet NaN 0x7fc00000.  Byte, SignedByte, Int16,
+ * UInt16: exact int32 sum, sum / count rounded half away from zero in integer
+ * arithmetic; Float32: fp32 sum from +0 in row-major box order, one fp32
+ * division by the count.  A result is stored as computed, even if it happens
+ * to equal the nodata value.  UInt32, Int32 and Float64: GSKYHIP_E_TYPE.
+ * Parity with GDAL's overviews is unpinned. */
+#define GSKYHIP_OVR_NEAREST 0
+#define GSKYHIP_OVR_AVERAGE 1
+/* level sizes, finest first (either array may be NULL); returns the level
+ * count (0..12) or GSKYHIP_E_ARG */
+int gskyhip_overview_levels(int xsize, int ysize, int min_size, int32_t *ovr_xsize, int32_t *ovr_ysize);
+/* src and ovr_out[k] are device pointers (ovr_out, ovr_xsize, ovr_ysize:
+ * host arrays of n_levels <= 12 entries, the first n_levels sizes that
+ * gskyhip_overview_levels gives); dtype GSKYHIP_BYTE with signed_byte, or
+ * GSKYHIP_SIGNEDBYTE, for int8.  Asynchronous on `stream`, no allocation:
+ * one launch per three levels.  Arguments are checked before any HIP call. */
+int gskyhip_build_overviews(const void *src, int dtype, int signed_byte, int xsize, int ysize,
+                            int has_nodata, double nodata, int method, int n_levels,
+                            void *const *ovr_out, const int32_t *ovr_xsize, const int32_t *ovr_ysize, void *stream);
+/* gskyhip_register_geotiff / _netcdf, and when the band came without
+ * overviews a pyramid of `method` down to `min_size` built into HBM the
+ * library owns (freed with the granule).  A file's own overviews always win:
+ * nothing is built over them.  GSKYHIP_E_TYPE (nothing registered) for a
+ * band type the pyramid does not cover.  The request is remembered: when the
+ * drop-in reads the file again (changed on disk, or evicted from the ingest
+ * cache) it builds the same pyramid, until the plain register call or
+ * gskyhip_unregister_all.
+ * warp_operation_fast's own ingest of an unregistered path does the same
+ * when GSKYHIP_BUILD_OVERVIEWS=nearest|average is in the environment (read
+ * once; GSKYHIP_OVERVIEW_MIN_SIZE optional; unset or empty: no pyramid; band
+ * types the pyramid does not cover are ingested without one). */
+int gskyhip_register_geotiff_ovr(const char *path, int band, int method, int min_size);
+int gskyhip_register_netcdf_ovr(const char *path, int band, int method, int min_size);
+
 /* ---- drop-in for the cgo entry point of the worker ----------------------- */
 /* Registers an HBM-resident granule under (path, band) so that the drop-in
  * below can find it (it replaces GDALOpenEx in warp.go:89-101; GeoTIFF files
@@ -380,6 +427,13 @@ int gskyhip_service_run(const char *socket_path, int max_batch, int window_us); 
 int gskyhip_service_register_granule(const char *socket_path, const char *path, int band,
                                      const gskyhip_granule *g, const void *data, const void *const *ovr_data,
                                      const char *srs);   /* data / ovr_data: host arrays, uploaded by the daemon */
+/* The same without overviews from the caller (g->n_ovr is ignored): the
+ * daemon builds the pyramid (gskyhip_build_overviews: method, min_size) in
+ * its own HBM after the upload.  A message kind of its own; the others are
+ * unchanged. */
+int gskyhip_service_register_granule_ovr(const char *socket_path, const char *path, int band,
+                                         const gskyhip_granule *g, const void *data, const char *srs,
+                                         int method, int min_size);
 int gskyhip_service_unregister_all(const char *socket_path);
 /* stats[4]: warp requests served, batches run, largest batch, registered granules */
 int gskyhip_service_stats(const char *socket_path, int64_t *stats);
