@@ -1,6 +1,6 @@
 // gsky_device.h -- device-side building blocks of the MI355X raster hot path.
 //
-// Projection math restates PROJ 6.1.1 (merc/webmerc, aea, gn_sinu, tmerc, lcc, polar stere, geos and the
+// Projection math restates PROJ 6.1.1 (merc/webmerc, aea, gn_sinu, tmerc, lcc, polar stere, geos, laea, cea and the
 // pj_fwd / pj_inv wrappers) and GDAL 3.0.1's GenImgProj transformer; numeric
 // conversions restate Go 1.12 on amd64.  All of it
 // is compiled with -ffp-contract=off so every double expression rounds once
@@ -392,6 +392,201 @@ __host__ __device__ inline __attribute__((noinline)) bool geos_inv(const gskyhip
   return true;
 }
 
+// Lambert azimuthal equal area, cylindrical equal area and Mercator on an
+// ellipsoid or a sphere (PROJ 6.1.1 laea.cpp / cea.cpp / merc.cpp, [ext];
+// Snyder, Map Projections: A Working Manual, sections 24, 10 and 7; pinned by
+// the EPSG Guidance Note 7-2, Snyder and EASE-Grid 2.0 worked examples and an
+// independent formulation in tests/test_equal_area.py / tests/test_merc.py).
+// Out of line, transcendentals through ext_*, for the register reason above.
+//
+// Field assignment (include/gskyhip.h): LAEA -- aspect in phi2 (0 north
+// polar, 1 south polar, 2 equatorial, 3 oblique), qp in n, rq in c, dd in dd,
+// xmf in rho0, ymf in ec, sinb1 in tm_qn, cosb1 in tm_zb; CEA -- qp in n, k0
+// in k0 (lat_ts kept in phi1); both -- the authalic series apa[3] in
+// tm_cgb[0..2].  Mercator -- k0 only.
+//
+// Two departures from PROJ, each below a centimetre on the ground:
+//  * the inverse authalic latitude takes PROJ's three-term series (which
+//    leaves about 8 mm) and then two Newton steps on q(phi), so inverse and
+//    forward close to well under a millimetre;
+//  * the failure rules at the poles / the antipode use 1e-12 rad where PROJ
+//    uses 1e-10: a point a tenth of a millimetre short of the rule succeeds.
+__host__ __device__ inline __attribute__((noinline)) double ext_asin(double a) { return asin(a); }
+__host__ __device__ inline __attribute__((noinline)) double ext_log(double a) { return log(a); }
+__host__ __device__ inline __attribute__((noinline)) double ext_exp(double a) { return exp(a); }
+
+constexpr int kLaeaNPole = 0, kLaeaSPole = 1, kLaeaEquit = 2, kLaeaObliq = 3;
+constexpr double kEaEps = 1.e-12;
+
+// pj_qsfn through the out-of-line helpers (qsfn() stays as Albers inlines it).
+__host__ __device__ inline double ea_qsfn(double sinphi, double e, double one_es) {
+  const double con = e * sinphi;
+  const double div1 = 1.0 - con * con, div2 = 1.0 + con;
+  if (div1 == 0.0 || div2 == 0.0) return HUGE_VAL;
+  return one_es * (sinphi / div1 - (.5 / e) * ext_log((1. - con) / div2));
+}
+
+// Geodetic latitude of the authalic latitude beta, whose sine times qp is qt.
+// Near a pole (cos phi < 1e-6) the series is left alone: its truncation error
+// vanishes there like sin(8 beta), and q(phi) is flat.
+__host__ __device__ inline double ea_authlat(const gskyhip_crs &c, double beta, double qt) {
+  const double t = beta + beta;
+  double phi = beta + c.tm_cgb[0] * ext_sin(t) + c.tm_cgb[1] * ext_sin(t + t) + c.tm_cgb[2] * ext_sin(t + t + t);
+#pragma unroll 1
+  for (int i = 0; i < 2; i++) {
+    const double sp = ext_sin(phi), cp = ext_cos(phi);
+    if (!(cp > 1.e-6)) break;
+    const double com = 1. - c.es * sp * sp;
+    phi -= (ea_qsfn(sp, c.e, c.one_es) - qt) * com * com / (2. * c.one_es * cp);
+  }
+  return phi;
+}
+
+// 1 + cos(z), z the arc from the centre (authalic latitude b1) to (lam, b),
+// as twice the haversine of the arc to the antipode: free of cancellation.
+__host__ __device__ inline double laea_antipode_b(double b1, double b, double lam) {
+  const double s = ext_sin(.5 * (b + b1)), ch = ext_cos(.5 * lam);
+  return 2. * (s * s + ext_cos(b) * ext_cos(b1) * ch * ch);
+}
+
+// false: the antipode of the centre.
+__host__ __device__ inline __attribute__((noinline)) bool laea_fwd(const gskyhip_crs &c, double lam, double phi,
+                                                                    double &xn, double &yn) {
+  const int mode = (int)c.phi2;
+  const double coslam = ext_cos(lam), sinlam = ext_sin(lam), sinphi = ext_sin(phi);
+  if (mode == kLaeaNPole || mode == kLaeaSPole) {
+    const bool south = mode == kLaeaSPole;
+    if (fabs(phi + c.phi0) < kEaEps) return false;
+    if (fabs(phi - c.phi0) < kEaEps) { xn = yn = 0.; return true; }   // the centre itself (qp - q rounds to 1e-16)
+    double b;
+    if (c.es != 0.) {
+      const double q = ea_qsfn(sinphi, c.e, c.one_es);
+      const double d = south ? c.n + q : c.n - q;
+      b = d >= 0. ? sqrt(d) : 0.;
+    } else {
+      const double h = kFortPi - phi * .5;
+      b = 2. * (south ? ext_cos(h) : ext_sin(h));
+    }
+    xn = b * sinlam;
+    yn = coslam * (south ? b : -b);
+    return true;
+  }
+  double sinb, cosb, xmf = 1., ymf = 1.;
+  if (c.es != 0.) {
+    sinb = ea_qsfn(sinphi, c.e, c.one_es) / c.n;
+    cosb = sqrt(1. - sinb * sinb);
+    xmf = c.rho0;
+    ymf = c.ec;
+  } else {
+    sinb = sinphi;
+    cosb = ext_cos(phi);
+  }
+  const double sinb1 = c.tm_qn, cosb1 = c.tm_zb;   // equatorial: 0, 1
+  double b = 1. + sinb1 * sinb + cosb1 * cosb * coslam;
+  if (b < 1.e-7) {   // within 3 km of the antipode
+    b = laea_antipode_b(ext_asin(sinb1), ext_asin(sinb), lam);
+    if (!(b > kEaEps * kEaEps)) return false;   // b = z^2 / 2 at the arc z from the antipode
+  }
+  b = sqrt(2. / b);
+  yn = ymf * b * (cosb1 * sinb - sinb1 * cosb * coslam);
+  xn = xmf * b * cosb * sinlam;
+  return true;
+}
+
+// false: outside the map's disc.
+__host__ __device__ inline __attribute__((noinline)) bool laea_inv(const gskyhip_crs &c, double xn, double yn,
+                                                                    double &lam, double &phi) {
+  const int mode = (int)c.phi2;
+  const bool ell = c.es != 0.;
+  double beta, sinbeta;
+  if (mode == kLaeaNPole || mode == kLaeaSPole) {
+    const bool south = mode == kLaeaSPole;
+    if (!south) yn = -yn;
+    const double q = xn * xn + yn * yn;
+    if (q == 0.) { lam = 0.; phi = c.phi0; return true; }
+    // sin(beta) = 1 - q / qp (sphere: qp = 2), as the half-angle of the
+    // authalic colatitude: no cancellation next to the pole
+    const double qp = ell ? c.n : 2.;
+    const double h = q / (qp + qp);
+    if (!(h <= 1.)) return false;
+    beta = kHalfPi - 2. * ext_asin(sqrt(h));
+    sinbeta = 1. - q / qp;
+    if (south) { beta = -beta; sinbeta = -sinbeta; }
+    lam = atan2(xn, yn);
+  } else {
+    const double sinb1 = c.tm_qn, cosb1 = c.tm_zb;
+    double rq = 1.;
+    if (ell) { xn /= c.dd; yn *= c.dd; rq = c.c; }
+    const double rho = hypot(xn, yn);
+    if (rho < 1.e-10) { lam = 0.; phi = c.phi0; return true; }
+    const double hz = .5 * rho / rq;
+    if (!(hz <= 1.)) return false;
+    const double z = 2. * ext_asin(hz);
+    const double cz = ext_cos(z), sz = ext_sin(z);
+    sinbeta = cz * sinb1 + yn * sz * cosb1 / rho;
+    yn = rho * cosb1 * cz - yn * sinb1 * sz;
+    xn *= sz;
+    if (sinbeta > 1.) sinbeta = 1.;
+    if (sinbeta < -1.) sinbeta = -1.;
+    beta = ext_asin(sinbeta);
+    lam = (xn == 0. && yn == 0.) ? 0. : atan2(xn, yn);
+  }
+  phi = ell ? ea_authlat(c, beta, c.n * sinbeta) : beta;
+  return true;
+}
+
+__host__ __device__ inline __attribute__((noinline)) bool cea_fwd(const gskyhip_crs &c, double lam, double phi,
+                                                                   double &xn, double &yn) {
+  const double sinphi = ext_sin(phi);
+  xn = c.k0 * lam;
+  yn = c.es != 0. ? .5 * ea_qsfn(sinphi, c.e, c.one_es) / c.k0 : sinphi / c.k0;
+  return true;
+}
+
+// false: beyond the pole line (by more than PROJ's 1e-10; within it, the pole).
+__host__ __device__ inline __attribute__((noinline)) bool cea_inv(const gskyhip_crs &c, double xn, double yn,
+                                                                   double &lam, double &phi) {
+  const bool ell = c.es != 0.;
+  double s = ell ? 2. * yn * c.k0 / c.n : yn * c.k0;
+  const double t = fabs(s);
+  if (!(t - 1.e-10 <= 1.)) return false;
+  if (t >= 1.) {
+    phi = s < 0. ? -kHalfPi : kHalfPi;
+  } else {
+    const double beta = ext_asin(s);
+    phi = ell ? ea_authlat(c, beta, c.n * s) : beta;
+  }
+  lam = xn / c.k0;
+  return true;
+}
+
+// false: a pole.
+__host__ __device__ inline __attribute__((noinline)) bool merc_e_fwd(const gskyhip_crs &c, double lam, double phi,
+                                                                      double &xn, double &yn) {
+  if (fabs(fabs(phi) - kHalfPi) <= kEaEps) return false;
+  xn = c.k0 * lam;
+  yn = -c.k0 * ext_log(lcc_tsfn(phi, ext_sin(phi), c.e));
+  return true;
+}
+
+__host__ __device__ inline __attribute__((noinline)) bool merc_e_inv(const gskyhip_crs &c, double xn, double yn,
+                                                                      double &lam, double &phi) {
+  const double ts = ext_exp(-yn / c.k0);   // pj_phi2
+  const double eccnth = .5 * c.e;
+  double Phi = kHalfPi - 2. * ext_atan(ts), dphi;
+  int i = 15;
+#pragma unroll 1
+  do {
+    const double con = c.e * ext_sin(Phi);
+    dphi = kHalfPi - 2. * ext_atan(ts * ext_pow((1. - con) / (1. + con), eccnth)) - Phi;
+    Phi += dphi;
+  } while (fabs(dphi) > 1.0e-10 && --i);
+  if (i <= 0) return false;
+  phi = Phi;
+  lam = xn / c.k0;
+  return true;
+}
+
 // pj_inv: CRS coordinates -> (lam, phi) in radians.
 __host__ __device__ inline bool crs_inverse(const gskyhip_crs &c, double x, double y, double &lam, double &phi) {
   if (x == HUGE_VAL || y == HUGE_VAL) return false;
@@ -441,6 +636,12 @@ __host__ __device__ inline bool crs_inverse(const gskyhip_crs &c, double x, doub
     if (!stere_inv(c, xn, yn, l, p)) return false;
   } else if (c.kind == GSKYHIP_CRS_GEOS) {  // geos.cpp e_inverse
     if (!geos_inv(c, xn, yn, l, p)) return false;
+  } else if (c.kind == GSKYHIP_CRS_LAEA) {  // laea.cpp e_inverse / s_inverse
+    if (!laea_inv(c, xn, yn, l, p)) return false;
+  } else if (c.kind == GSKYHIP_CRS_CEA) {  // cea.cpp e_inverse / s_inverse
+    if (!cea_inv(c, xn, yn, l, p)) return false;
+  } else if (c.kind == GSKYHIP_CRS_MERC) {  // merc.cpp e_inverse
+    if (!merc_e_inv(c, xn, yn, l, p)) return false;
   } else {
     return false;
   }
@@ -487,6 +688,12 @@ __host__ __device__ inline bool crs_forward(const gskyhip_crs &c, double lam, do
     if (!stere_fwd(c, lam, phi, xn, yn)) return false;
   } else if (c.kind == GSKYHIP_CRS_GEOS) {  // geos.cpp e_forward
     if (!geos_fwd(c, lam, phi, xn, yn)) return false;
+  } else if (c.kind == GSKYHIP_CRS_LAEA) {  // laea.cpp e_forward / s_forward
+    if (!laea_fwd(c, lam, phi, xn, yn)) return false;
+  } else if (c.kind == GSKYHIP_CRS_CEA) {  // cea.cpp e_forward / s_forward
+    if (!cea_fwd(c, lam, phi, xn, yn)) return false;
+  } else if (c.kind == GSKYHIP_CRS_MERC) {  // merc.cpp e_forward
+    if (!merc_e_fwd(c, lam, phi, xn, yn)) return false;
   } else {
     return false;
   }

@@ -210,6 +210,99 @@ int geos_setup(gskyhip_crs *c, double h, bool sweep_x) {
   return 0;
 }
 
+// pj_authset() of PROJ 6.1.1: the three-term series authalic -> geodetic
+// latitude (Snyder 3-18), into tm_cgb[0..2] (gsky_device.h ea_authlat).
+void authalic_setup(gskyhip_crs *c) {
+  const double es = c->es, es2 = es * es, es3 = es2 * es;
+  c->tm_cgb[0] = es * (1 / 3.0) + es2 * (31 / 180.0) + es3 * (517 / 5040.0);
+  c->tm_cgb[1] = es2 * (23 / 360.0) + es3 * (251 / 3780.0);
+  c->tm_cgb[2] = es3 * (761 / 45360.0);
+}
+
+// laea.cpp setup() of PROJ 6.1.1: the aspect from lat_0, and on an ellipsoid
+// qp, rq, dd, xmf, ymf and the authalic latitude of the centre; assigned as
+// include/gskyhip.h documents.  phi0 / lam0 / x0 / y0 set by the caller.
+int laea_setup(gskyhip_crs *c) {
+  const double t = std::fabs(c->phi0);
+  if (!(t <= kHalfPi + 1e-10)) return GSKYHIP_E_CRS;
+  c->kind = GSKYHIP_CRS_LAEA;
+  c->k0 = 1.0;
+  c->phi1 = 0.0;
+  int mode;
+  if (std::fabs(t - kHalfPi) < 1e-10) {
+    mode = c->phi0 < 0 ? kLaeaSPole : kLaeaNPole;
+    c->phi0 = c->phi0 < 0 ? -kHalfPi : kHalfPi;
+  } else if (t < 1e-10) {
+    mode = kLaeaEquit;
+  } else {
+    mode = kLaeaObliq;
+  }
+  c->phi2 = mode;
+  c->n = 2.0; c->c = 1.0; c->dd = 1.0; c->rho0 = 1.0; c->ec = 1.0;
+  c->tm_qn = 0.0; c->tm_zb = 1.0;   // sinb1, cosb1 (equatorial)
+  if (c->es != 0.) {
+    c->n = h_qsfn(1., c->e, c->one_es);   // qp
+    authalic_setup(c);
+    if (mode == kLaeaEquit) {
+      c->c = std::sqrt(.5 * c->n);
+      c->dd = 1. / c->c;
+      c->rho0 = 1.;
+      c->ec = .5 * c->n;
+    } else if (mode == kLaeaObliq) {
+      c->c = std::sqrt(.5 * c->n);
+      const double sinphi = std::sin(c->phi0);
+      c->tm_qn = h_qsfn(sinphi, c->e, c->one_es) / c->n;
+      c->tm_zb = std::sqrt(1. - c->tm_qn * c->tm_qn);
+      c->dd = std::cos(c->phi0) / (std::sqrt(1. - c->es * sinphi * sinphi) * c->c * c->tm_zb);
+      c->ec = c->c / c->dd;
+      c->rho0 = c->c * c->dd;
+    }
+  } else if (mode == kLaeaObliq) {
+    c->tm_qn = std::sin(c->phi0);
+    c->tm_zb = std::cos(c->phi0);
+  }
+  return 0;
+}
+
+// k0 of a cylindrical projection true to scale at lat_ts (pj_msfn).
+double ts_k0(const gskyhip_crs *c, double lat_ts) {
+  const double s = std::sin(lat_ts);
+  return std::cos(lat_ts) / std::sqrt(1. - c->es * s * s);
+}
+
+// cea.cpp setup() of PROJ 6.1.1: k0 from +lat_ts, else +k_0; qp.
+int cea_setup(gskyhip_crs *c, bool has_ts, double lat_ts, double k0) {
+  if (has_ts && !(std::fabs(lat_ts) < kHalfPi)) return GSKYHIP_E_CRS;
+  if (!has_ts && !(k0 > 0)) return GSKYHIP_E_CRS;
+  c->kind = GSKYHIP_CRS_CEA;
+  c->phi0 = 0.0; c->phi2 = 0.0;
+  c->phi1 = has_ts ? lat_ts : 0.0;
+  c->k0 = has_ts ? ts_k0(c, lat_ts) : k0;
+  c->n = 2.0;
+  if (c->es != 0.) {
+    c->n = h_qsfn(1., c->e, c->one_es);
+    authalic_setup(c);
+  }
+  return 0;
+}
+
+// merc.cpp setup() of PROJ 6.1.1: k0 from +lat_ts (2SP), else +k_0 (1SP).
+// The sphere with k0 = 1 stays GSKYHIP_CRS_WEBMERC (the callers see to it).
+int merc_setup(gskyhip_crs *c, bool has_ts, double lat_ts, double k0) {
+  if (has_ts && !(std::fabs(lat_ts) < kHalfPi)) return GSKYHIP_E_CRS;
+  if (!has_ts && !(k0 > 0)) return GSKYHIP_E_CRS;
+  c->kind = GSKYHIP_CRS_MERC;
+  c->phi0 = 0.0; c->phi2 = 0.0;
+  c->phi1 = has_ts ? std::fabs(lat_ts) : 0.0;
+  c->k0 = has_ts ? ts_k0(c, c->phi1) : k0;
+  return 0;
+}
+
+// Mercator on a sphere, true to scale at the equator: the web-mercator kind.
+bool merc_is_web(const gskyhip_crs *c, bool has_ts, double lat_ts, double k0) {
+  return c->es == 0.0 && (!has_ts || lat_ts == 0.0) && k0 == 1.0;
+}
+
 // utm.cpp setup: zone -> central meridian, k0 0.9996, false easting 500 km,
 // false northing 10,000 km in the south.
 int utm_setup(gskyhip_crs *c, int zone, bool south) {
@@ -273,7 +366,50 @@ int crs_epsg(int code, gskyhip_crs *c) {
     c->phi1 = -18.0 * kD2R_h; c->phi2 = -36.0 * kD2R_h; c->phi0 = 0.0; c->lam0 = 134.0 * kD2R_h;
     return lcc_setup(c);
   }
+  if (code == 3035) {   // ETRS89-extended / LAEA Europe
+    set_ellps(c, 6378137.0, 298.257222101);
+    c->phi0 = 52.0 * kD2R_h; c->lam0 = 10.0 * kD2R_h; c->x0 = 4321000.0; c->y0 = 3210000.0;
+    return laea_setup(c);
+  }
+  if (code == 6931 || code == 6932 || code == 3408 || code == 3409) {   // EASE-Grid 2.0 / EASE-Grid North, South
+    if (code > 6000) set_ellps(c, 6378137.0, 298.257223563);
+    else set_ellps(c, 6371228.0, 0.0);
+    c->phi0 = ((code == 6931 || code == 3408) ? 90.0 : -90.0) * kD2R_h;
+    return laea_setup(c);
+  }
+  if (code == 6933 || code == 3410) {   // EASE-Grid 2.0 / EASE-Grid Global
+    if (code == 6933) set_ellps(c, 6378137.0, 298.257223563);
+    else set_ellps(c, 6371228.0, 0.0);
+    return cea_setup(c, true, 30.0 * kD2R_h, 1.0);
+  }
+  if (code == 3395 || code == 3832) {   // WGS 84 / World Mercator, PDC Mercator
+    set_ellps(c, 6378137.0, 298.257223563);
+    c->lam0 = (code == 3832 ? 150.0 : 0.0) * kD2R_h;
+    return merc_setup(c, false, 0.0, 1.0);
+  }
   return GSKYHIP_E_CRS;
+}
+
+// The ellipsoid of a PROJ string of the equal-area / Mercator families: the
+// forms crs_proj4 takes (+ellps / +datum, +a +rf, +R), and +a +b, +a +es.
+void proj4_ellps(const std::string &s, gskyhip_crs *c, double a, double rf, double R) {
+  set_ellps(c, a, rf);
+  if (R > 0 || rf != 0) return;
+  bool has_b = false, has_es = false;
+  const double b = proj_param(s, "+b", 0, &has_b), es = proj_param(s, "+es", 0, &has_es);
+  if (has_es && es >= 0 && es < 1) c->es = es;
+  else if (has_b && b > 0) c->es = 1.0 - (b * b) / (a * a);
+  else return;
+  c->e = std::sqrt(c->es);
+  c->one_es = 1.0 - c->es;
+}
+
+// +lat_ts | +k_0 (or +k) of +proj=cea / +proj=merc.
+void proj4_ts_k0(const std::string &s, bool &has_ts, double &lat_ts, double &k0) {
+  bool has_k = false;
+  lat_ts = proj_param(s, "+lat_ts", 0, &has_ts) * kD2R_h;
+  k0 = proj_param(s, "+k_0", 1.0, &has_k);
+  if (!has_k) k0 = proj_param(s, "+k", 1.0);
 }
 
 int crs_proj4(const std::string &s, gskyhip_crs *c) {
@@ -296,8 +432,28 @@ int crs_proj4(const std::string &s, gskyhip_crs *c) {
   if (s.find("+proj=longlat") != std::string::npos || s.find("+proj=latlong") != std::string::npos) {
     c->kind = GSKYHIP_CRS_LONGLAT; set_ellps(c, a, rf); return 0;
   }
-  if (s.find("+proj=webmerc") != std::string::npos || (s.find("+proj=merc") != std::string::npos && R > 0)) {
+  if (s.find("+proj=webmerc") != std::string::npos) {
     c->kind = GSKYHIP_CRS_WEBMERC; set_ellps(c, a, 0.0); return 0;
+  }
+  if (s.find("+proj=merc") != std::string::npos) {   // merc.cpp; the k0 = 1 sphere is the web-mercator kind
+    proj4_ellps(s, c, a, rf, R);
+    bool has_ts = false;
+    double ts = 0, k0 = 1;
+    proj4_ts_k0(s, has_ts, ts, k0);
+    if (merc_is_web(c, has_ts, ts, k0)) { c->kind = GSKYHIP_CRS_WEBMERC; set_ellps(c, a, 0.0); return 0; }
+    return merc_setup(c, has_ts, ts, k0);
+  }
+  if (s.find("+proj=laea") != std::string::npos) {   // laea.cpp
+    proj4_ellps(s, c, a, rf, R);
+    if (!(std::fabs(c->phi0) <= kHalfPi + 1e-10)) return GSKYHIP_E_CRS;
+    return laea_setup(c);
+  }
+  if (s.find("+proj=cea") != std::string::npos) {   // cea.cpp
+    proj4_ellps(s, c, a, rf, R);
+    bool has_ts = false;
+    double ts = 0, k0 = 1;
+    proj4_ts_k0(s, has_ts, ts, k0);
+    return cea_setup(c, has_ts, ts, k0);
   }
   if (s.find("+proj=aea") != std::string::npos) {
     c->kind = GSKYHIP_CRS_AEA; set_ellps(c, a, rf);
@@ -456,6 +612,48 @@ int parse_srs(const char *srs, gskyhip_crs *c) {
       sweep_x = sw != std::string::npos && (close == std::string::npos || sw < close);
     }
     return geos_setup(c, param("satellite_height", 0), sweep_x);
+  }
+  const bool w_laea = s.find("PROJECTION[\"Lambert_Azimuthal_Equal_Area\"]") != std::string::npos;
+  const bool w_cea = s.find("PROJECTION[\"Cylindrical_Equal_Area\"]") != std::string::npos;
+  const bool w_m1 = s.find("PROJECTION[\"Mercator_1SP\"]") != std::string::npos;
+  const bool w_m2 = s.find("PROJECTION[\"Mercator_2SP\"]") != std::string::npos;
+  if (w_laea || w_cea || w_m1 || w_m2) {   // WKT1 (GDAL) equal-area / Mercator: a known top-level code, else its parameters
+    const size_t au = s.rfind("AUTHORITY[\"EPSG\",\"");   // (EPSG:3857 is a Mercator_1SP node over the WGS 84 spheroid)
+    if (au != std::string::npos && crs_epsg(std::atoi(s.c_str() + au + 18), c) == 0) return 0;
+    auto param = [&](const char *name, double dflt) {
+      const std::string k = std::string("PARAMETER[\"") + name + "\",";
+      const size_t p = s.find(k);
+      return p == std::string::npos ? dflt : std::strtod(s.c_str() + p + k.size(), nullptr);
+    };
+    double a = 6378137.0, rf = 298.257223563;
+    const size_t p = s.find("SPHEROID[");
+    if (p != std::string::npos) {
+      const size_t q = s.find(',', p);
+      if (q != std::string::npos) {
+        char *end = nullptr;
+        a = std::strtod(s.c_str() + q + 1, &end);
+        if (end && *end == ',') rf = std::strtod(end + 1, nullptr);
+      }
+    }
+    std::memset(c, 0, sizeof(*c));
+    c->k0 = 1.0;
+    set_ellps(c, a, rf);
+    c->x0 = param("false_easting", 0);
+    c->y0 = param("false_northing", 0);
+    if (w_laea) {
+      const double lat0 = param("latitude_of_center", 0);
+      if (!(std::fabs(lat0) <= 90.0)) return GSKYHIP_E_CRS;
+      c->phi0 = lat0 * kD2R_h;
+      c->lam0 = param("longitude_of_center", 0) * kD2R_h;
+      return laea_setup(c);
+    }
+    c->lam0 = param("central_meridian", 0) * kD2R_h;
+    if (w_cea) return cea_setup(c, true, param("standard_parallel_1", 0) * kD2R_h, 1.0);
+    const bool has_ts = w_m2;
+    const double ts = w_m2 ? param("standard_parallel_1", 0) * kD2R_h : 0.0;
+    const double k0 = w_m2 ? 1.0 : param("scale_factor", 1.0);
+    if (merc_is_web(c, has_ts, ts, k0)) { c->kind = GSKYHIP_CRS_WEBMERC; return 0; }
+    return merc_setup(c, has_ts, ts, k0);
   }
   const bool lcc2 = s.find("PROJECTION[\"Lambert_Conformal_Conic_2SP\"]") != std::string::npos;
   const bool lcc1 = s.find("PROJECTION[\"Lambert_Conformal_Conic_1SP\"]") != std::string::npos;

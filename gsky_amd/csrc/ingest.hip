@@ -1154,6 +1154,32 @@ std::string nc_cf_srs(const Nc &f, const NcVar &v) {
                       fe, fn, ell, sweep_x ? "x" : "y");
         return buf;
       }
+      if (name == "lambert_azimuthal_equal_area") {   // netcdfdataset.h:211; ellipsoid or sphere
+        std::snprintf(buf, sizeof(buf), "+proj=laea +lat_0=%.17g +lon_0=%.17g +x_0=%.17g +y_0=%.17g %s",
+                      num(m, "latitude_of_projection_origin", 0, 0), num(m, "longitude_of_projection_origin", 0, 0),
+                      fe, fn, ell);
+        return buf;
+      }
+      // cylindrical equal area (and the reference's alias, netcdfdataset.h:208) and
+      // Mercator: the standard parallel, else the scale factor
+      const bool cf_cea = name == "lambert_cylindrical_equal_area" || name == "cylindrical_equal_area";
+      if (cf_cea || name == "mercator") {
+        const double cm = cf_cea ? num(m, "longitude_of_central_meridian", 0, 0)
+                                 : num(m, "longitude_of_projection_origin", 0, 0);
+        // the sphere true to scale at the equator is the web-mercator kind, which
+        // the CF route has never served (the file's EPSG code does): unchanged
+        if (!cf_cea && sphere &&
+            (has(m, "standard_parallel") ? num(m, "standard_parallel", 0, 0) == 0.0
+                                         : num(m, "scale_factor_at_projection_origin", 0, 1.0) == 1.0))
+          return "?";
+        if (has(m, "standard_parallel"))
+          std::snprintf(buf, sizeof(buf), "+proj=%s +lat_ts=%.17g +lon_0=%.17g +x_0=%.17g +y_0=%.17g %s",
+                        cf_cea ? "cea" : "merc", num(m, "standard_parallel", 0, 0), cm, fe, fn, ell);
+        else
+          std::snprintf(buf, sizeof(buf), "+proj=%s +k_0=%.17g +lon_0=%.17g +x_0=%.17g +y_0=%.17g %s",
+                        cf_cea ? "cea" : "merc", num(m, "scale_factor_at_projection_origin", 0, 1.0), cm, fe, fn, ell);
+        return buf;
+      }
       if (name == "sinusoidal" && sphere) {
         std::snprintf(buf, sizeof(buf), "+proj=sinu +lon_0=%.17g +x_0=%.17g +y_0=%.17g %s",
                       num(m, "longitude_of_central_meridian", 0, num(m, "longitude_of_projection_origin", 0, 0)),

@@ -346,6 +346,29 @@ bool cf_mapping(int epsg, const char *srs_in, std::vector<Att> &atts, bool &geog
       atts.push_back(att_f64("false_northing", {c.y0}));
       ellps();
       return true;
+    case GSKYHIP_CRS_LAEA:
+      atts.push_back(att_str("grid_mapping_name", "lambert_azimuthal_equal_area"));
+      atts.push_back(att_f64("latitude_of_projection_origin", {c.phi2 == 0.0 ? 90.0 : c.phi2 == 1.0 ? -90.0 : c.phi0 * rad}));
+      atts.push_back(att_f64("longitude_of_projection_origin", {c.lam0 * rad}));
+      atts.push_back(att_f64("false_easting", {c.x0}));
+      atts.push_back(att_f64("false_northing", {c.y0}));
+      ellps();
+      return true;
+    case GSKYHIP_CRS_CEA:
+    case GSKYHIP_CRS_MERC: {   // the standard parallel where k0 derives from it, else the scale factor
+      const bool cea = c.kind == GSKYHIP_CRS_CEA;
+      atts.push_back(att_str("grid_mapping_name", cea ? "lambert_cylindrical_equal_area" : "mercator"));
+      const double s1 = std::sin(c.phi1);
+      if (c.k0 == std::cos(c.phi1) / std::sqrt(1. - c.es * s1 * s1))
+        atts.push_back(att_f64("standard_parallel", {c.phi1 * rad}));
+      else
+        atts.push_back(att_f64("scale_factor_at_projection_origin", {c.k0}));
+      atts.push_back(att_f64(cea ? "longitude_of_central_meridian" : "longitude_of_projection_origin", {c.lam0 * rad}));
+      atts.push_back(att_f64("false_easting", {c.x0}));
+      atts.push_back(att_f64("false_northing", {c.y0}));
+      ellps();
+      return true;
+    }
     default:
       return false;
   }

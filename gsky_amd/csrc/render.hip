@@ -704,6 +704,59 @@ __device__ void plan_pair(const PlanArgs &a, int p, double *sx, double *sy, int 
   }
   if (lane != 0) return;
 
+  // A Lambert azimuthal equal area source that holds a pole (the EASE-Grid
+  // North / South grids hold theirs at the centre), into a cylindrical
+  // north-up destination: every edge sample transforms, so GDAL takes the
+  // extent of the outline alone, which for such a granule is the low
+  // latitudes -- the ground between the outline and the pole, most of the
+  // granule, stays outside the window.  Deliberately not reproduced, for this
+  // family only: with a pole inside the granule the x extent is closed to the
+  // destination's periodic edges (every meridian ends there) and the y extent
+  // to the pole's side of the destination.
+  if (err == 0 && t.reproject && !t.gl && t.src.kind == GSKYHIP_CRS_LAEA &&
+      (t.dst.kind == GSKYHIP_CRS_WEBMERC || t.dst.kind == GSKYHIP_CRS_LONGLAT) && t.dst_gt[2] == 0.0 &&
+      t.dst_gt[4] == 0.0) {
+    const bool ll = t.dst.kind == GSKYHIP_CRS_LONGLAT;
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) {
+      double xn, yn;
+      if (!laea_fwd(t.src, 0.0, s ? -kHalfPi : kHalfPi, xn, yn)) continue;   // (the antipode of the centre)
+      const double X = t.src.a * xn + t.src.x0, Y = t.src.a * yn + t.src.y0;
+      const double px = t.src_igt[0] + X * t.src_igt[1] + Y * t.src_igt[2];
+      const double py = t.src_igt[3] + X * t.src_igt[4] + Y * t.src_igt[5];
+      if (!(px > 0.0 && px < nInX && py > 0.0 && py < nInY)) continue;
+      const double half = ll ? 180.0 : kPi * t.dst.a * t.dst.k0, mid = ll ? 0.0 : t.dst.x0;
+      const double pl = t.dst_igt[0] + (mid - half) * t.dst_igt[1], pr = t.dst_igt[0] + (mid + half) * t.dst_igt[1];
+      ext[0] = fmin(ext[0], fmin(pl, pr));
+      ext[2] = fmax(ext[2], fmax(pl, pr));
+      const double row = ll ? t.dst_igt[3] + (s ? -90.0 : 90.0) * t.dst_igt[5]
+                            : (((s == 0) == (t.dst_gt[5] < 0.0)) ? -1.0e9 : 1.0e9);
+      ext[1] = fmin(ext[1], row);
+      ext[3] = fmax(ext[3], row);
+    }
+  }
+  // A cylindrical equal area or ellipsoidal Mercator source (north-up) that
+  // reaches beyond +-180 degrees (the EASE-Grid 2.0 Global grid's published
+  // half extent lies 5 mm beyond; a PDC Mercator granule over the Pacific),
+  // into a cylindrical north-up destination: PROJ wraps the samples beyond,
+  // and GDAL's extent stops at the last sample before the edge, up to a
+  // twentieth of the granule short of it (the geostationary seam above).
+  // Deliberately not reproduced, for these families only: the x extent is
+  // closed to the destination's periodic edges.
+  if (err == 0 && t.reproject && !t.gl && (t.src.kind == GSKYHIP_CRS_CEA || t.src.kind == GSKYHIP_CRS_MERC) &&
+      (t.dst.kind == GSKYHIP_CRS_WEBMERC || t.dst.kind == GSKYHIP_CRS_LONGLAT) && t.dst_gt[2] == 0.0 &&
+      t.dst_gt[4] == 0.0 && t.src_gt[2] == 0.0 && t.src_gt[4] == 0.0) {
+    const double la = (t.src_gt[0] - t.src.x0) * t.src.ra / t.src.k0 + t.src.lam0;
+    const double lb = (t.src_gt[0] + nInX * t.src_gt[1] - t.src.x0) * t.src.ra / t.src.k0 + t.src.lam0;
+    if (fmin(la, lb) < -(kPi + 1e-12) || fmax(la, lb) > kPi + 1e-12) {
+      const bool ll = t.dst.kind == GSKYHIP_CRS_LONGLAT;
+      const double half = ll ? 180.0 : kPi * t.dst.a * t.dst.k0, mid = ll ? 0.0 : t.dst.x0;
+      const double pl = t.dst_igt[0] + (mid - half) * t.dst_igt[1], pr = t.dst_igt[0] + (mid + half) * t.dst_igt[1];
+      ext[0] = fmin(ext[0], fmin(pl, pr));
+      ext[2] = fmax(ext[2], fmax(pl, pr));
+    }
+  }
+
   // ---- overview pick (warp.go:156-198)
   const void *band = g.data;
   int bandX = g.xsize, bandY = g.ysize;

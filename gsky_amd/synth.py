@@ -390,6 +390,87 @@ def config_geos(n: int = 1100, res: float = 10000.0, origins=None, tiles=None, t
     return SynthConfig("GEOS", granules, "EPSG:3857", list(tiles), pairs, [""], (0.0, 0.0, 10000.0, 0), PALETTE_GSKY)
 
 
+# ---------------------------------------------------------------- equal-area / Mercator families
+INDEX_MOD = 181   # 181 * 181 - 1 = 32760 fits int16
+
+
+def index_granule(nx: int, ny: int) -> np.ndarray:
+    """int16 values that name their element: (row % 181) * 181 + (col % 181).
+    A pick known to within 90 pixels is recovered exactly (index_decode)."""
+    col = (np.arange(nx) % INDEX_MOD).astype(np.int16)
+    row = (np.arange(ny) % INDEX_MOD).astype(np.int16)
+    return row[:, None] * np.int16(INDEX_MOD) + col[None, :]
+
+
+def index_decode(v, near_x, near_y):
+    """(col, row) of index_granule values `v` picked within 90 pixels of (near_x, near_y)."""
+    v = np.asarray(v, np.int64)
+    nx, ny = np.floor(near_x).astype(np.int64), np.floor(near_y).astype(np.int64)
+    half = INDEX_MOD // 2
+    col = nx + (v % INDEX_MOD - nx + half) % INDEX_MOD - half
+    row = ny + (v // INDEX_MOD - ny + half) % INDEX_MOD - half
+    return col, row
+
+
+def _config_grid(name, srs, nx, ny, res, origin, tiles, pairs=None) -> SynthConfig:
+    """One north-up int16 index_granule of nx x ny pixels of `res` metres with
+    its top-left corner at `origin`, nodata -1, under EPSG:3857 `tiles`."""
+    x0, y0 = origin
+    x1, y1 = x0 + nx * res, y0 - ny * res
+    poly = "POLYGON ((%.1f %.1f,%.1f %.1f,%.1f %.1f,%.1f %.1f,%.1f %.1f))" % (x0, y0, x1, y0, x1, y1, x0, y1, x0, y0)
+    g = SynthGranule(index_granule(nx, ny), [float(x0), float(res), 0.0, float(y0), 0.0, -float(res)], srs, -1.0,
+                     1577836800.0, poly)
+    if pairs is None:
+        pairs = [[0] for _ in tiles]
+    return SynthConfig(name, [g], "EPSG:3857", list(tiles), pairs, [""], (0.0, 0.0, float(INDEX_MOD ** 2), 0), PALETTE_GSKY)
+
+
+def _z1_world_tiles(tile_px):
+    return [(_webmerc_tile_bbox(1, x, y), tile_px, tile_px) for y in range(2) for x in range(2)]
+
+
+def config_laea_europe(n: int = 1000, res: float = 1000.0, tiles_per_side: int = 3, tile_px: int = 256) -> SynthConfig:
+    """One n x n granule in ETRS89-extended / LAEA Europe (EPSG:3035, oblique
+    aspect) centred on 50 N 10 E, under tiles_per_side^2 EPSG:3857 tiles over
+    its bounding box."""
+    from .tiles import crs_transform
+    cx, cy, _ = crs_transform("EPSG:4326", "EPSG:3035", [10.0], [50.0])
+    origin = (round(float(cx[0])) - 0.5 * n * res, round(float(cy[0])) + 0.5 * n * res)
+    cfg = _config_grid("LAEA", "EPSG:3035", n, n, res, origin, [])
+    fp = _footprint_merc(cfg.granules[0], 64)
+    bbox = (float(np.floor(fp[0])), float(np.floor(fp[1])), float(np.ceil(fp[2])), float(np.ceil(fp[3])))
+    cfg.tiles = _grid_tiles(bbox, tiles_per_side, tiles_per_side, tile_px)
+    cfg.pairs = [[0] for _ in cfg.tiles]
+    return cfg
+
+
+def config_ease2_north(srs: str = "EPSG:6931", tile_px: int = 256) -> SynthConfig:
+    """The 25-km EASE-Grid 2.0 North grid (720 x 720, origin (-9000000,
+    9000000), polar aspect; the whole northern hemisphere) under the four z1
+    world tiles: the two southern ones see nothing of it."""
+    return _config_grid("EASE2N", srs, 720, 720, 25000.0, (-9000000.0, 9000000.0), _z1_world_tiles(tile_px))
+
+
+def config_ease2_global(tile_px: int = 256) -> SynthConfig:
+    """The 36-km EASE-Grid 2.0 Global grid (EPSG:6933, 964 x 406, to 85.0445664
+    degrees of latitude) under the four z1 world tiles."""
+    return _config_grid("EASE2G", "EPSG:6933", 964, 406, 36032.220840584, (-17367530.45, 7314540.83),
+                        _z1_world_tiles(tile_px))
+
+
+def config_pdc_mercator(n: int = 1024, res: float = 5000.0, tile_px: int = 256) -> SynthConfig:
+    """One n x n granule in PDC Mercator (EPSG:3832, central meridian 150 E)
+    centred on 180 E at the equator, under two EPSG:3857 tiles that meet at
+    the antimeridian: one ending at x = +20037508.34, one starting at
+    -20037508.34.  Both are filled from the one granule."""
+    from .tiles import crs_transform
+    cx, _, _ = crs_transform("EPSG:4326", "EPSG:3832", [180.0], [0.0])
+    origin = (round(float(cx[0])) - 0.5 * n * res, 0.5 * n * res)
+    edge, half = 20037508.342789244, 0.5 * n * res * 1.1
+    tiles = [((edge - 2 * half, -half, edge, half), tile_px, tile_px), ((-edge, -half, -edge + 2 * half, half), tile_px, tile_px)]
+    return _config_grid("PDCMERC", "EPSG:3832", n, n, res, origin, tiles)
+
+
 def subset(cfg: SynthConfig, tile_ids) -> SynthConfig:
     """The same config restricted to some tiles (for bounded CPU samples)."""
     tiles = [cfg.tiles[i] for i in tile_ids]

@@ -78,6 +78,39 @@ extern "C" {
                                     * whose transform fails over whole regions:  *
                                     * forward beyond the limb, inverse off the   *
                                     * disc (ok = 0 in gskyhip_crs_transform)     */
+#define GSKYHIP_CRS_LAEA 8         /* Lambert azimuthal equal area, ellipsoid or *
+                                    * sphere, all four aspects: EASE-Grid 2.0    *
+                                    * North / South (EPSG:6931 / 6932), ETRS89-   *
+                                    * extended LAEA Europe (EPSG:3035), the       *
+                                    * spherical EASE grids (EPSG:3408 / 3409),    *
+                                    * +proj=laea, WKT1 Lambert_Azimuthal_Equal_   *
+                                    * Area, CF lambert_azimuthal_equal_area.      *
+                                    * lat_0 in phi0; aspect in phi2 (0 north      *
+                                    * polar, 1 south polar, 2 equatorial, 3       *
+                                    * oblique); qp in n, rq in c, dd in dd, xmf   *
+                                    * in rho0, ymf in ec; and in the slots no     *
+                                    * non-tmerc kind uses: sinb1 in tm_qn, cosb1  *
+                                    * in tm_zb, the authalic series apa[0..2] in  *
+                                    * tm_cgb[0..2].  All derive from a, es and    *
+                                    * phi0.  The forward fails at the antipode of *
+                                    * the centre, the inverse outside the disc    */
+#define GSKYHIP_CRS_CEA 9          /* cylindrical equal area, ellipsoid or sphere: *
+                                    * EASE-Grid 2.0 Global (EPSG:6933), the       *
+                                    * spherical global EASE grid (EPSG:3410),     *
+                                    * +proj=cea +lat_ts | +k_0, WKT1 Cylindrical_ *
+                                    * Equal_Area, CF lambert_cylindrical_equal_   *
+                                    * area.  k0 (from lat_ts, else given) in k0,  *
+                                    * lat_ts in phi1, qp in n, apa[0..2] in       *
+                                    * tm_cgb[0..2].  The inverse fails beyond the *
+                                    * pole line                                   */
+#define GSKYHIP_CRS_MERC 10        /* Mercator on an ellipsoid (1SP / 2SP), or on *
+                                    * a sphere with lat_ts != 0 or k_0 != 1:      *
+                                    * World Mercator (EPSG:3395), PDC Mercator    *
+                                    * (EPSG:3832), +proj=merc, WKT1 Mercator_1SP  *
+                                    * / Mercator_2SP, CF mercator.  k0 (from      *
+                                    * lat_ts, else given) in k0, |lat_ts| in phi1. *
+                                    * The forward fails at the poles.  The        *
+                                    * spherical k0 = 1 case stays WEBMERC         */
 
 typedef struct {
     int32_t kind;
