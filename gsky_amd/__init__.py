@@ -1,6 +1,6 @@
 """gsky_amd -- MI355X-native GSKY raster hot path.
 
-warp (reprojection + NN/bilinear resampling) -> time-ordered nodata-aware
+warp (reprojection + NN/bilinear/cubic resampling) -> time-ordered nodata-aware
 mosaic -> byte scaling -> palette/RGBA, and the drill zonal reduction, as
 hand-written HIP kernels for gfx950 behind a C-ABI (include/gskyhip.h,
 libgskyhip.so).  See DESIGN.md.

@@ -1350,7 +1350,7 @@ __device__ __forceinline__ void plan_row(const PlanArgs &a, int p, const PairPla
     }
   }
   a.rows[(long)p * a.max_h + row] = rec;
-  a.rowfix[(long)p * a.max_h + row] = row_fix(rec, n, a.resample != GSKYHIP_RESAMPLE_BILINEAR);
+  a.rowfix[(long)p * a.max_h + row] = row_fix(rec, n, a.resample == GSKYHIP_RESAMPLE_NEAREST);
 }
 
 // Workgroups of one pair (blockIdx.x: pair, blockIdx.y: 256-row chunk): the
@@ -2274,7 +2274,9 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
                   const uint8_t *ramp, uint8_t *rgba_out, void *canvas_out, int phase) {
   if (n_out != 1 && n_out != 3) return GSKYHIP_E_ARG;  // ogc_encoders.go:135-136
   for (int k = 0; k < n_out; k++) if (out_ns[k] < 0 || out_ns[k] >= 4) return GSKYHIP_E_ARG;
-  if (rc.resample != GSKYHIP_RESAMPLE_NEAREST && rc.resample != GSKYHIP_RESAMPLE_BILINEAR) return GSKYHIP_E_ARG;
+  if (rc.resample != GSKYHIP_RESAMPLE_NEAREST && rc.resample != GSKYHIP_RESAMPLE_BILINEAR &&
+      rc.resample != GSKYHIP_RESAMPLE_CUBIC)
+    return GSKYHIP_E_ARG;
   // rgba_out == NULL: canvases only (WCS GetCoverage, FusionUnscale, ows.go:728)
   const bool autom = rgba_out && sp.offset == 0.0 && sp.scale == 0.0 && sp.clip == 0.0;
   if ((autom || !rgba_out) && !canvas_out) return GSKYHIP_E_ARG;
@@ -2324,7 +2326,11 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
   const int vt = single_value_type(rc.value_types);
   const bool bil = rc.resample == GSKYHIP_RESAMPLE_BILINEAR;
   int lds_mode = -1;
-  if (vt && n_out == 1 && !autom) {
+  if (rc.resample == GSKYHIP_RESAMPLE_CUBIC) {
+    // cubic: float32 canvases without a mask layer have a band kernel
+    // (render_cub_kernel); every other combination runs the generic kernels
+    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask) lds_mode = kCanvas | kCubic;
+  } else if (vt && n_out == 1 && !autom) {
     if (a.write_rgba && !canvas_out) lds_mode = bil ? kBilinear : 0;
     else if (!rgba_out && canvas_out) lds_mode = kCanvas | (bil ? kBilinear : 0);
   }
@@ -2479,6 +2485,9 @@ int launch_warp_windows(const RenderCall &rc, int32_t *bbox_out, int32_t *dtype_
   const dim3 grid((unsigned)((nthreads + 255) / 256));
   if (rc.resample == GSKYHIP_RESAMPLE_BILINEAR)
     hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_BILINEAR>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
+                       cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
+  else if (rc.resample == GSKYHIP_RESAMPLE_CUBIC)
+    hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_CUBIC>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
                        cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
   else
     hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_NEAREST>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,

@@ -206,7 +206,7 @@ struct RenderArgs {
   MinMax *minmax;        // n_tiles * 3
   int write_rgba;
   const EntryD *entries;
-  int lds_mode;          // typed band kernels: kBilinear | kCanvas bits of the call
+  int lds_mode;          // typed band kernels: kBilinear | kCanvas | kCubic bits of the call
   const int64_t *cov_offsets;  // canvas mode: per tile element offset into one image (NULL: slots)
   int64_t cov_stride;          // ... and that image's row stride (elements)
 };
@@ -334,6 +334,56 @@ __device__ __forceinline__ bool bil_fetch(const EntryD &e, double sx, double sy,
   return true;
 }
 
+// One 1-D cubic convolution of GWKCubicResample4Sample (GDAL 3.0.1), every
+// operation in the written order (the numpy rule of tests/test_cubic.py
+// evaluates the same sequence).
+__device__ __forceinline__ double cubic_conv(double t, double f0, double f1, double f2, double f3) {
+  const double t2 = t * t;
+  const double t3 = t2 * t;
+  return f1 + 0.5 * (t * (f2 - f0) + t2 * (2.0 * f0 - 5.0 * f1 + 4.0 * f2 - f3) + t3 * (3.0 * (f1 - f2) + f3 - f0));
+}
+
+// The 4 x 4 taps of a cubic sample lie inside an nx x ny band (tested on the
+// floored coordinates as doubles: no integer conversion of a far coordinate).
+__device__ __forceinline__ bool cubic_inside(double fx, double fy, int nx, int ny) {
+  return fx >= 1.0 && fx + 2.0 < (double)nx && fy >= 1.0 && fy + 2.0 < (double)ny;
+}
+
+// GWKCubicResample4Sample of one window pixel in type T (GSKYHIP_RESAMPLE_CUBIC,
+// gskyhip.h): the 16 taps in fp64; a tap outside the band or equal to the
+// band's nodata hands the pixel to bil_fetch().  false -> window fill.
+template <typename T>
+__device__ __forceinline__ bool cub_fetch(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
+  const double fx = floor(sx - 0.5), fy = floor(sy - 0.5);
+  if (!cubic_inside(fx, fy, e.band_x, e.band_y)) return bil_fetch<T>(e, sx, sy, v);
+  const int iX = (int)fx, iY = (int)fy;
+  const double tx = sx - 0.5 - fx, ty = sy - 0.5 - fy;
+  const T *band = (const T *)e.band + ((long)(iY - 1) * e.band_x + (iX - 1));
+  double h[4];
+  bool anynd = false;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    double f[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      f[i] = bil_tap<T>(band[(long)j * e.band_x + i]);
+      anynd = anynd || (e.has_nodata && (f[i] == e.nodata64 || (e.nodata64 != e.nodata64 && f[i] != f[i])));
+    }
+    h[j] = cubic_conv(tx, f[0], f[1], f[2], f[3]);
+  }
+  if (anynd) return bil_fetch<T>(e, sx, sy, v);
+  const double r = cubic_conv(ty, h[0], h[1], h[2], h[3]);
+  if constexpr (std::is_same<T, float>::value) v = (float)r;
+  else v = gdal_copy_to(floor(r + 0.5), e.out_dtype).i;
+  return true;
+}
+// cub_fetch() behind a call, for the generic kernels: inlined at each of a
+// wave's 16 pixels the body is too large for their loops to unroll.
+template <typename T>
+__device__ __noinline__ bool cub_fetch_call(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
+  return cub_fetch<T>(e, sx, sy, v);
+}
+
 // Full per-pixel path (exact points, descend): only complex tiles and the
 // drop-in window kernel run it.
 __device__ __noinline__ bool descend_coords(const Xform &t, int xoff, double yrow, int n0, const double *v,
@@ -439,7 +489,15 @@ __device__ __forceinline__ bool mask_fast_pair(const EntryD *__restrict__ ents, 
   double sx, sy;
   int32_t v = 0;
   bool ok = false;
-  if (lin_coords(rows[m.row_base + my], pool, mx, sx, sy)) {   // false: failed transform -> fill
+  if (!lin_coords(rows[m.row_base + my], pool, mx, sx, sy)) {   // failed transform -> fill
+  } else if (RES == GSKYHIP_RESAMPLE_CUBIC) {   // the mask raster warps by the data's rule
+    switch (m.out_dtype) {
+      case GSKYHIP_BYTE: ok = cub_fetch_call<uint8_t>(m, sx, sy, v); break;
+      case GSKYHIP_SIGNEDBYTE: ok = cub_fetch_call<int8_t>(m, sx, sy, v); break;
+      case GSKYHIP_INT16: ok = cub_fetch_call<int16_t>(m, sx, sy, v); break;
+      default: ok = cub_fetch_call<uint16_t>(m, sx, sy, v); break;
+    }
+  } else {
     switch (m.out_dtype) {
       case GSKYHIP_BYTE: ok = nn_fetch<uint8_t>(m, sx, sy, v); break;
       case GSKYHIP_SIGNEDBYTE: ok = nn_fetch<int8_t>(m, sx, sy, v); break;
@@ -461,6 +519,7 @@ __device__ __forceinline__ bool mask_fast(const EntryD *__restrict__ ents, const
 
 constexpr int kLdsBandRows = 16;   // rows per block of render_lds_kernel
 constexpr int kBilinear = 4, kCanvas = 8;   // render_lds_kernel modes (RenderArgs.lds_mode)
+constexpr int kCubic = 16;                  // float32 canvases by cubic convolution: render_cub_kernel (render_cub.h)
 
 // The typed band kernels (render_lds.hip) for value type `vt`.
 void launch_band_kernels(const RenderArgs &a, int vt, bool mask, int n_items, hipStream_t s);

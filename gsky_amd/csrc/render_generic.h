@@ -73,6 +73,32 @@ __device__ __noinline__ Val bilinear_value(const PairPlan &pp, double sx, double
   return gdal_copy_to(floor(r + 0.5), pp.out_dtype);
 }
 
+// GWKCubicResample4Sample semantics (GSKYHIP_RESAMPLE_CUBIC, gskyhip.h): the
+// 4 x 4 taps around floor(s - 0.5), rows first, in fp64; bilinear_value()
+// where a tap lies outside the band or holds the band's nodata.
+__device__ __noinline__ Val cubic_value(const PairPlan &pp, double sx, double sy) {
+  const double fx = floor(sx - 0.5), fy = floor(sy - 0.5);
+  if (!cubic_inside(fx, fy, pp.band_x, pp.band_y)) return bilinear_value(pp, sx, sy);
+  const int iX = (int)fx, iY = (int)fy;
+  const double tx = sx - 0.5 - fx, ty = sy - 0.5 - fy;
+  const long base = (long)(iY - 1) * pp.band_x + (iX - 1);
+  double h[4];
+  bool anynd = false;
+  for (int j = 0; j < 4; j++) {
+    double f[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      f[i] = load_dbl(pp.band, pp.src_dtype, base + (long)j * pp.band_x + i);
+      anynd = anynd || (pp.has_nodata && (f[i] == pp.nodata || (pp.nodata != pp.nodata && f[i] != f[i])));
+    }
+    h[j] = cubic_conv(tx, f[0], f[1], f[2], f[3]);
+  }
+  if (anynd) return bilinear_value(pp, sx, sy);
+  const double r = cubic_conv(ty, h[0], h[1], h[2], h[3]);
+  if (pp.out_dtype == GSKYHIP_FLOAT32) { Val o; o.f = (float)r; return o; }
+  return gdal_copy_to(floor(r + 0.5), pp.out_dtype);
+}
+
 // Warped value of window pixel (i,row) of a pair: the source value or the
 // window's nodata fill (warp.go:246-247, 271-344).
 template <bool GENERAL, int RES>
@@ -82,6 +108,7 @@ __device__ __forceinline__ Val warped_value(const PairPlan &pp, const RowRec &rr
   const bool ok = src_coords<GENERAL>(rr, pool, xf, pp.xoff, pp.yoff, pp.w, i, row, sx, sy);
   if (!ok) return pp.fill;
   if (RES == GSKYHIP_RESAMPLE_BILINEAR) return bilinear_value(pp, sx, sy);
+  if (RES == GSKYHIP_RESAMPLE_CUBIC) return cubic_value(pp, sx, sy);
   if (sx < 0 || sy < 0) return pp.fill;
   const double ax = sx + 1.0e-10, ay = sy + 1.0e-10;
   if (ax >= 2147483647.0 || ay >= 2147483647.0) return pp.fill;
@@ -343,6 +370,10 @@ __device__ __forceinline__ void render_fast_t(const RenderArgs &a, const EntryD 
             v = fillv;
             V got;
             if (in && okq[q] && bil_fetch<T>(e, sx, sy, got)) v = got;
+          } else if (RES == GSKYHIP_RESAMPLE_CUBIC) {
+            v = fillv;
+            V got;
+            if (in && okq[q] && cub_fetch_call<T>(e, sx, sy, got)) v = got;
           } else {
             v = nn_px<T>(e, sx, sy, in && okq[q], fillv);
           }
@@ -481,6 +512,9 @@ static void dispatch_render_t(const RenderArgs &a, int resample, bool mask, dim3
   if (resample == GSKYHIP_RESAMPLE_BILINEAR) {
     if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_BILINEAR, true>(a, grid, general_only, s);
     else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_BILINEAR, false>(a, grid, general_only, s);
+  } else if (resample == GSKYHIP_RESAMPLE_CUBIC) {
+    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBIC, true>(a, grid, general_only, s);
+    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBIC, false>(a, grid, general_only, s);
   } else {
     if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_NEAREST, true>(a, grid, general_only, s);
     else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_NEAREST, false>(a, grid, general_only, s);

@@ -927,12 +927,18 @@ void launch_nn_t(const RenderArgs &a, bool mask, hipStream_t s) {
 }
 
 void launch_bil(const RenderArgs &a, int n_items, hipStream_t s);   // render_bil.h, band_f32.hip
+void launch_cub(const RenderArgs &a, hipStream_t s);                // render_cub.h, band_f32.hip
 
-// Band kernel of one call: bilinear float canvases without a mask layer ->
-// render_bil_kernel; other bilinear work -> render_lds_kernel; nearest
-// neighbour -> render_nn_kernel.
+// Band kernel of one call: cubic float canvases -> render_cub_kernel
+// (launch_render sets kCubic for float32 canvases without a mask layer only);
+// bilinear float canvases without a mask layer -> render_bil_kernel; other
+// bilinear work -> render_lds_kernel; nearest neighbour -> render_nn_kernel.
 template <typename T>
 void launch_band_t(const RenderArgs &a, bool mask, int n_items, hipStream_t s) {
+  if ((a.lds_mode & kCubic) != 0) {
+    if constexpr (std::is_same<T, float>::value) launch_cub(a, s);
+    return;
+  }
   if ((a.lds_mode & kBilinear) != 0) {
     if constexpr (std::is_same<T, float>::value) {
       if (!mask && (a.lds_mode & kCanvas)) {

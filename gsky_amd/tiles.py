@@ -213,6 +213,8 @@ class TileBatch:
         """Warp + merge + scale + RGBA for every tile.  Returns the RGBA
         tensor (n_tiles, H, W, 4); with canvas=True also the typed canvases
         (n_tiles, n_out, H*W*4 bytes).  rgba=False renders canvases only (WCS).
+        resample: 0 nearest, 1 bilinear, 2 cubic convolution
+        (_lib.RESAMPLE_*; GDAL's 4-sample formulas, include/gskyhip.h).
         phase 1 / 2 run the planning / render kernels alone (same arguments)."""
         n_out = len(self.namespaces)
         if n_out not in (1, 3):
@@ -297,7 +299,9 @@ class TileBatch:
         """WCS GetCoverage: every tile's typed canvas of the first namespace
         written straight into `out` (a 2-D tensor of the canvas type) with
         tile t's top-left at flat element offset offsets[t]
-        (gskyhip_render_coverage; no per-tile slots, no assembly copy)."""
+        (gskyhip_render_coverage; no per-tile slots, no assembly copy).
+        resample: 0 nearest, 1 bilinear, 2 cubic convolution; float32
+        coverages have a band kernel for each."""
         if out.dim() != 2:
             raise ValueError("coverage must be 2-D")
         offs = offsets if isinstance(offsets, torch.Tensor) else torch.tensor(list(offsets), dtype=torch.int64)
@@ -361,7 +365,8 @@ class TileBatch:
     # ------------------------------------------------------------------ windows
     def warp_windows(self, resample: int = 0):
         """The FlexRasters of tile_grpc.go:228-241: per pair
-        (window tensor, bbox [xoff, yoff, w, h], type name, nodata)."""
+        (window tensor, bbox [xoff, yoff, w, h], type name, nodata).
+        resample: 0 nearest, 1 bilinear, 2 cubic convolution."""
         npairs = self.n_pairs
         bbox = torch.zeros((max(1, npairs), 4), dtype=torch.int32, device=self.device)
         dt = torch.zeros(max(1, npairs), dtype=torch.int32, device=self.device)

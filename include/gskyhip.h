@@ -332,6 +332,18 @@ int64_t gskyhip_render_workspace_size(int n_tiles, int n_pairs, int max_tile_hei
 
 #define GSKYHIP_RESAMPLE_NEAREST 0
 #define GSKYHIP_RESAMPLE_BILINEAR 1
+/* Cubic convolution, GDAL 3.0.1 GWKCubicResample4Sample: with (sx, sy) the
+ * source coordinate (pixel centres at +0.5), iX = floor(sx - 0.5), iY =
+ * floor(sy - 0.5), tx = sx - 0.5 - iX, ty = sy - 0.5 - iY and
+ *   CC(t, f0, f1, f2, f3) = f1 + 0.5 * (t * (f2 - f0) + t^2 * (2 f0 - 5 f1 +
+ *                           4 f2 - f3) + t^3 * (3 (f1 - f2) + f3 - f0)),
+ * the sample is CC(ty, h(-1), h(0), h(1), h(2)), h(j) = CC(tx, f(iX - 1, iY +
+ * j), ..., f(iX + 2, iY + j)); Float32 results are cast, integer results go
+ * through floor(r + 0.5) and saturate.  Where one of the 16 taps lies outside
+ * the band or equals the band's nodata the pixel takes the bilinear rule's
+ * value.  Accepted by gskyhip_render_tiles / _phase / _typed,
+ * gskyhip_render_coverage and gskyhip_warp_windows. */
+#define GSKYHIP_RESAMPLE_CUBIC 2
 
 /* Warp + merge + scale + palette for a batch of tiles, replacing per tile:
  * gRPC warp fan-out (tile_grpc.go:200-289 -> warp.go:82-382), RasterMerger
