@@ -36,17 +36,14 @@ int launch_extent(const gskyhip_granule *granules, int n, const gskyhip_crs *crs
                   int32_t *out, int32_t *status, hipStream_t s);
 int launch_warp_windows(const RenderCall &c, int32_t *bbox_out, int32_t *dtype_out, double *nodata_out,
                         void *win_out, int64_t win_stride);
-// bytesRead of the drop-in for the pairs of a planned call, job k = pair k
-// (one request each): stats[4k + 2] receives it.  `jobs` (device) give each
-// job's block size, its bitmap words and its xsrc / bitmap regions (byte
-// offsets into `scratch`, 4-byte aligned, xsrc max_px words); max_px bounds
-// every pair's window (w * h).
+// bytesRead of the drop-in for the pairs of a warp batch (launch_warp_jobs),
+// job k = pair k (one request each).  `jobs` (device) give each job's block
+// size, its bitmap words and its xsrc / bitmap regions (byte offsets into
+// `scratch`, 4-byte aligned, xsrc max_px words).
 struct BlockStatsJob {
   int32_t bx, by, n_words, _pad;
   int64_t xsrc_off, bits_off;
 };
-int launch_block_stats_batch(const RenderCall &c, const BlockStatsJob *jobs, int n_jobs, int64_t max_px,
-                             void *scratch, int32_t *stats);
 
 // Per pair of a planned batch: granule, picked level (x, y), element bytes,
 // source footprint [x0, y0, x1, y1) at that level (8 int32 per pair, device).
@@ -64,6 +61,7 @@ struct WarpResult {
 // the window into outs[job] (device addresses: staging or registered host
 // memory) with its bytesRead inputs in the same pass, then results[job].
 // max_px bounds every pair's window (w * h).  3 launches after planning.
+// Nearest neighbour only: GSKYHIP_E_ARG for any other c.resample.
 int launch_warp_jobs(const RenderCall &c, const BlockStatsJob *jobs, int64_t max_px, void *scratch,
                      int32_t *stats, uint8_t *const *outs, WarpResult *results);
 

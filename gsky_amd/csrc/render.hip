@@ -1685,17 +1685,13 @@ __global__ __launch_bounds__(256) void warp_window_kernel(const PairPlan *pairs,
   else ((uint32_t *)o)[idx] = v.u;
 }
 
-// bytesRead of the drop-in (warp.go:278-347), pair 0: per window pixel the
-// reference's two tests -- the cache heuristic's x test (success, dx >= 0,
-// iSrcX < srcXSize; no dy test) and the full gather test -- plus the set of
-// source blocks that valid pixels touch.
-// warp.go:281-347 bytesRead of every (single-pair) request of a warp batch,
-// blockIdx.y = job = pair: per valid pixel the source x (xsrc, for the
-// cache decision), the first valid pixel, the valid count and the touched
-// block bits.  The counters are reduced per workgroup (ballots, one atomic
-// each) and the bits per wave (a lane ORs its block only where it differs
-// from the previous lane's), so neighbouring pixels do not serialize on one
-// address.
+// bytesRead of the drop-in (warp.go:278-347) for every (single-pair) request
+// of a warp batch, job = pair: per window pixel the reference's two tests --
+// the cache heuristic's x test (success, dx >= 0, iSrcX < srcXSize; no dy
+// test) and the full gather test -- give the source x (xsrc, for the cache
+// decision), the first valid pixel, the valid count and the bits of the
+// source blocks that valid pixels touch.  This kernel clears a job's bits and
+// counters; warp_job_kernel fills them and warp_job_resolve_kernel reads them.
 __global__ __launch_bounds__(256) void block_stats_init_kernel(const BlockStatsJob *jobs, char *scratch,
                                                                int32_t *stats) {
   const BlockStatsJob J = jobs[blockIdx.x];
@@ -1707,149 +1703,26 @@ __global__ __launch_bounds__(256) void block_stats_init_kernel(const BlockStatsJ
   }
 }
 
-__global__ __launch_bounds__(256) void block_stats_kernel(const PairPlan *pairs, const Xform *xforms,
-                                                          const RowRec *rows, const Leaf *pool, int max_h,
-                                                          const BlockStatsJob *jobs, char *scratch, int32_t *stats) {
-  const int job = blockIdx.y;
-  const PairPlan &pp = pairs[job];
-  const BlockStatsJob J = jobs[job];
-  int32_t *xsrc = (int32_t *)(scratch + J.xsrc_off);
-  uint32_t *bits = (uint32_t *)(scratch + J.bits_off);
-  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = (long)pp.w * pp.h;
-  bool valid = false;
-  int ix = 0, iy = 0;
-  if (gid < n) {
-    const int row = (int)(gid / pp.w), i = (int)(gid % pp.w);
-    double sx, sy;
-    const bool ok = src_coords<true>(rows[(int64_t)job * max_h + row], pool, xforms + job, pp.xoff, pp.yoff, pp.w, i,
-                                     row, sx, sy);
-    int xs = -1;
-    if (ok && !(sx < 0)) {
-      const double ax = sx + 1.0e-10;
-      if (ax < 2147483647.0) {
-        ix = (int)ax;
-        if (ix < pp.band_x) xs = ix;
-      }
-    }
-    if (xs >= 0 && !(sy < 0)) {
-      const double ay = sy + 1.0e-10;
-      if (ay < 2147483647.0) {
-        iy = (int)ay;
-        valid = iy < pp.band_y;
-      }
-    }
-    xsrc[gid] = xs;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long bal = __ballot(valid);
-  __shared__ int s_first[4], s_count[4];
-  if (lane == 0) {
-    s_first[wave] = bal ? (int)(gid + __ffsll((long long)bal) - 1) : 0x7FFFFFFF;
-    s_count[wave] = __popcll(bal);
-  }
-  int bx = J.bx;
-  if (bx <= 0) bx = pp.band_x;        // default block: one scanline of the chosen level
-  const int nxb = (pp.band_x + bx - 1) / bx;
-  const long long blk = valid ? (long long)(ix / bx) + (long long)(iy / J.by) * nxb : -1;
-  const long long prev = __shfl_up(blk, 1, 64);
-  if (valid && (lane == 0 || prev != blk)) atomicOr(&bits[blk >> 5], 1u << (blk & 31));
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int first = s_first[0], count = s_count[0];
-    for (int w = 1; w < 4; w++) { first = min(first, s_first[w]); count += s_count[w]; }
-    if (count > 0) {
-      atomicMin(&stats[4 * job], first);
-      atomicAdd(&stats[4 * job + 1], count);
-    }
-  }
-}
-
-// warp.go:281-313 (the cache decision at the first valid pixel) and 347, a
-// workgroup (one thread) per job.
-__global__ void block_stats_resolve_kernel(const PairPlan *pairs, const BlockStatsJob *jobs, const char *scratch,
-                                           int32_t *stats_all) {
-  if (threadIdx.x != 0) return;
-  const int job = blockIdx.x;
-  const PairPlan &pp = pairs[job];
-  const BlockStatsJob J = jobs[job];
-  const int32_t *xsrc = (const int32_t *)(scratch + J.xsrc_off);
-  const uint32_t *bits = (const uint32_t *)(scratch + J.bits_off);
-  int32_t *stats = stats_all + 4 * job;
-  int bx = J.bx;
-  if (bx <= 0) bx = pp.band_x;
-  const int i0 = stats[0];
-  if (i0 == 0x7FFFFFFF) { stats[2] = 0; return; }
-  const int r0 = i0 / pp.w, c0 = i0 % pp.w;
-  const int prev = xsrc[i0];
-  int curr = -1;
-  for (int c = c0 + 1; c < pp.w; c++) {
-    const int v = xsrc[(long)r0 * pp.w + c];
-    if (v >= 0) { curr = v; break; }
-  }
-  if (curr < prev) curr = prev;
-  const int stride = curr - prev;
-  const bool cache = stride >= 0 && stride < bx;
-  long nread = 0;
-  if (cache) {
-    for (int k = 0; k < J.n_words; k++) nread += __popc(bits[k]);
-  } else {
-    nread = stats[1];   // one GDALReadBlock per valid pixel (warp.go:319-322)
-  }
-  // C int arithmetic of warp.go:347 (wraps like the reference's 32-bit int)
-  const long long b = (long long)bx * J.by * type_size(pp.src_dtype) * nread;
-  stats[2] = (int32_t)(uint32_t)(unsigned long long)b;
-}
-
-// One window pixel of a job: its value (warped_value's rules, warp.go:271-344)
-// and the bytesRead inputs (block_stats_kernel's, warp.go:281-347).
+// One window pixel of a job from one evaluation of its source coordinates:
+// its value (warped_value's: sampled_value() or the window fill) and the
+// bytesRead inputs (warp.go:281-347): xs, the source x where the cache
+// heuristic's x test passes (else -1), and valid with (ix, iy) where the full
+// gather test does.
 template <int RES>
 __device__ __forceinline__ Val warp_job_pixel(const PairPlan &pp, const RowRec &rr, const Leaf *pool, const Xform *xf,
                                               int i, int row, int &xs, bool &valid, int &ix, int &iy) {
   double sx, sy;
   const bool ok = src_coords<true>(rr, pool, xf, pp.xoff, pp.yoff, pp.w, i, row, sx, sy);
-  // bytesRead: the cache heuristic's x test and the full gather test
-  xs = -1;
-  valid = false;
-  ix = 0;
-  iy = 0;
-  if (ok && !(sx < 0)) {
-    const double ax = sx + 1.0e-10;
-    if (ax < 2147483647.0) {
-      ix = (int)ax;
-      if (ix < pp.band_x) xs = ix;
-    }
-  }
-  if (xs >= 0 && !(sy < 0)) {
-    const double ay = sy + 1.0e-10;
-    if (ay < 2147483647.0) {
-      iy = (int)ay;
-      valid = iy < pp.band_y;
-    }
-  }
-  // the window value, exactly as warped_value<true, RES>
-  Val v = pp.fill;
-  if (ok) {
-    if (RES == GSKYHIP_RESAMPLE_BILINEAR) {
-      v = bilinear_value(pp, sx, sy);
-    } else if (!(sx < 0 || sy < 0)) {
-      const double ax = sx + 1.0e-10, ay = sy + 1.0e-10;
-      if (!(ax >= 2147483647.0 || ay >= 2147483647.0)) {
-        const int jx = (int)ax, jy = (int)ay;
-        if (jx < pp.band_x && jy < pp.band_y) {
-          v = load_val(pp.band, pp.src_dtype, (long)jy * pp.band_x + jx);
-          if (pp.out_dtype == GSKYHIP_SIGNEDBYTE) v.i = (int32_t)(int8_t)(uint8_t)v.i;
-        }
-      }
-    }
-  }
-  return v;
+  const bool okx = ok && nn_axis(sx, pp.band_x, ix);
+  xs = okx ? ix : -1;
+  valid = okx && nn_axis(sy, pp.band_y, iy);
+  return ok ? sampled_value<RES>(pp, sx, sy) : pp.fill;
 }
 
 // The per-node service's warp batch (warp_batch_launch, host.cpp): for every
 // request (job = pair) its window values AND its bytesRead inputs from ONE
 // source-coordinate evaluation per pixel -- round 4 ran warp_window_kernel
-// and block_stats_kernel, each deriving the same coordinates again.  The
+// and a bytesRead kernel, each deriving the same coordinates again.  The
 // window goes straight to the job's destination `outs[job]`: a device staging
 // slot, or the requesting worker's shared reply arena (host memory registered
 // with HIP, written over PCIe: no read-back copy).  PX pixels per thread
@@ -1959,8 +1832,9 @@ __global__ __launch_bounds__(256) void warp_job_kernel(const PairPlan *pairs, co
   }
 }
 
-// bytesRead (block_stats_resolve_kernel's rules) and the job's reply record
-// (bbox, dtype, nodata, overview-rescaled geotransform): one thread per job.
+// bytesRead (warp.go:281-313: the cache decision at the first valid pixel,
+// and 347) and the job's reply record (bbox, dtype, nodata, overview-rescaled
+// geotransform): one thread per job.
 __global__ void warp_job_resolve_kernel(const PairPlan *pairs, const BlockStatsJob *jobs, const char *scratch,
                                         int32_t *stats_all, int n_jobs, WarpResult *res) {
   const int job = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1989,8 +1863,9 @@ __global__ void warp_job_resolve_kernel(const PairPlan *pairs, const BlockStatsJ
     if (cache) {
       for (int k = 0; k < J.n_words; k++) nread += __popc(bits[k]);
     } else {
-      nread = stats[1];
+      nread = stats[1];   // one GDALReadBlock per valid pixel (warp.go:319-322)
     }
+    // C int arithmetic of warp.go:347 (wraps like the reference's 32-bit int)
     const long long b = (long long)bx * J.by * type_size(pp.src_dtype) * nread;
     br = (int32_t)(uint32_t)(unsigned long long)b;
   }
@@ -2351,20 +2226,6 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
   return hipGetLastError() == hipSuccess ? 0 : GSKYHIP_E_HIP;
 }
 
-int launch_block_stats_batch(const RenderCall &rc, const BlockStatsJob *jobs, int n_jobs, int64_t max_px,
-                             void *scratch, int32_t *stats) {
-  if (n_jobs <= 0) return 0;
-  const Carve cv = carve(rc.workspace, rc.n_tiles, rc.n_pairs, rc.max_h);
-  hipStream_t s = rc.stream;
-  hipLaunchKernelGGL(block_stats_init_kernel, dim3(n_jobs), dim3(256), 0, s, jobs, (char *)scratch, stats);
-  if (max_px > 0)
-    hipLaunchKernelGGL(block_stats_kernel, dim3((unsigned)((max_px + 255) / 256), n_jobs), dim3(256), 0, s, cv.pairs,
-                       cv.xforms, cv.rows, cv.pool, rc.max_h, jobs, (char *)scratch, stats);
-  hipLaunchKernelGGL(block_stats_resolve_kernel, dim3(n_jobs), dim3(64), 0, s, cv.pairs, jobs,
-                     (const char *)scratch, stats);
-  return hipGetLastError() == hipSuccess ? 0 : GSKYHIP_E_HIP;
-}
-
 int launch_pair_footprint(void *workspace, int n_tiles, int n_pairs, int max_h, int32_t *out, hipStream_t s) {
   if (n_pairs <= 0) return 0;
   const Carve cv = carve(workspace, n_tiles, n_pairs, max_h);
@@ -2437,6 +2298,7 @@ int launch_pair_touched(void *workspace, int n_tiles, int n_pairs, int max_h, in
 
 int launch_warp_jobs(const RenderCall &rc, const BlockStatsJob *jobs, int64_t max_px, void *scratch,
                      int32_t *stats, uint8_t *const *outs, WarpResult *results) {
+  if (rc.resample != GSKYHIP_RESAMPLE_NEAREST) return GSKYHIP_E_ARG;   // the service warps nearest only
   Carve cv;
   int rcode = plan_all(rc, cv);
   if (rcode || rc.n_pairs <= 0) return rcode;
@@ -2453,12 +2315,9 @@ int launch_warp_jobs(const RenderCall &rc, const BlockStatsJob *jobs, int64_t ma
       const int v = e ? atoi(e) : 8;
       return v == 1 || v == 4 ? v : 8;
     }();
-    const int px = rc.resample == GSKYHIP_RESAMPLE_BILINEAR ? 1 : env_px;
+    const int px = env_px;
     const dim3 grid((unsigned)((max_px + 256 * px - 1) / (256 * px)), n);
-    if (rc.resample == GSKYHIP_RESAMPLE_BILINEAR)
-      hipLaunchKernelGGL(warp_job_kernel<GSKYHIP_RESAMPLE_BILINEAR>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
-                         cv.rows, cv.pool, rc.max_h, jobs, (char *)scratch, stats, outs);
-    else if (px == 4)
+    if (px == 4)
       hipLaunchKernelGGL((warp_job_kernel<GSKYHIP_RESAMPLE_NEAREST, 4>), grid, dim3(256), 0, s, cv.pairs, cv.xforms,
                          cv.rows, cv.pool, rc.max_h, jobs, (char *)scratch, stats, outs);
     else if (px == 8)

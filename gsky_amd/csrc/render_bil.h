@@ -20,7 +20,7 @@
 //     relative (north_star's bar: 1e-4), 17 % faster (render 0.94 vs
 //     1.13 ms, profiles/r03b_ab_c3.jsonl);
 //     W = double (A/B build, GSKYHIP_BIL_F32=0): the weights and sums in
-//     fp64, the expressions of bil_sample() (render_lds.h);
+//     fp64, the expressions of bilinear_rule() (resample.h);
 //   * the fp64 division runs only for pixels whose accDiv is not exactly 1
 //     (a tap dropped): the others take accR as it is.
 #pragma once
@@ -33,9 +33,10 @@ namespace gsky {
 // x + 1 of the upper source row, t1 of the lower; rx / ry the weights of x
 // and y) and its fold into the canvas value c: the four weights sum to 1
 // within fp32 rounding, so the sample is accR unless a tap holds nodata
-// (then the taps are dropped and the weights renormalised: bil_sample's
-// rule).  The dropped-tap sums are formed for every pixel (a few selects);
-// only their division sits behind a branch.  NaN nodata: the fp64 path.
+// (then the taps are dropped and the weights renormalised: bil4_renorm()'s
+// sums, resample.h).  The dropped-tap sums are formed for every pixel (a few
+// selects); only their division sits behind a branch.  NaN nodata: the fp64
+// path.
 template <typename WT>
 __device__ __forceinline__ void bil_fold4(u32x2 t0, u32x2 t1, WT rx, WT ry, int ic, int lim, float nd, float ndf,
                                           bool hnd, float fillv, bool fill_mode, float &c) {
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(256, WPS) void render_bil_kernel(RenderArgs a, cons
         // A nodata that no float32 equals drops no tap, so a sample over taps
         // that all hold (float)nodata is the merge nodata itself and has to
         // come out as exactly that value, which fp32 weights miss by an ulp:
-        // bil_sample's fp64 expressions, one pixel at a time (rare bands).
+        // bilinear_rule()'s fp64 expressions, one pixel at a time (rare bands).
         const float *bandp = (const float *)uniform_ptr(e.band);
 #pragma unroll
         for (int q = 0; q < kNnPx; q++) {
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(256, WPS) void render_bil_kernel(RenderArgs a, cons
           double sx = 0.0, sy = 0.0;
           ok = ok && lin_coords(*rr, pool, ok ? ic : 0, sx, sy);
           float v = fillv, got;
-          if (ok && bil_sample<float>(bandp, bx, by, hnd, nd64, GSKYHIP_FLOAT32, sx, sy, got)) v = got;
+          if (ok && band_bil<float>(bandp, bx, by, hnd, nd64, GSKYHIP_FLOAT32, sx, sy, got)) v = got;
           const bool take = ((unsigned)ic < (unsigned)lim) & (v != nd) & (!fill_mode | (c[q] == nd));
           c[q] = take ? v : c[q];
         }
@@ -347,19 +348,7 @@ __global__ __launch_bounds__(256, WPS) void render_bil_kernel(RenderArgs a, cons
               }
               anynd = anynd & hnd;
               float v = (float)accR;
-              if (anynd) {   // drop the nodata taps and renormalise (bil_sample's rule)
-                WT aR = (WT)0.0, aD = (WT)0.0;
-#pragma unroll
-                for (int kk = 0; kk < 4; kk++) {
-                  const WT w = wx[kk & 1] * wy[kk >> 1];
-                  const bool use = !(nd_nan ? (tv[kk] != tv[kk]) : (tv[kk] == ndf));
-                  aD += use ? w : (WT)0.0;
-                  aR += use ? (WT)tv[kk] * w : (WT)0.0;
-                }
-                v = fillv;
-                if (aD == (WT)1.0) v = (float)aR;
-                else if (aD >= (WT)0.00001) v = (float)(aR / aD);
-              }
+              if (anynd) v = bil4_renorm<WT>(tv, wx, wy, nd_nan, ndf, fillv);   // drop the nodata taps and renormalise
               const int ic = ic0 + 64 * (h + q);
               const bool take = ((unsigned)ic < (unsigned)lim) & (v != nd) & (!fill_mode | (c[h + q] == nd));
               c[h + q] = take ? v : c[h + q];

@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "gsky_device.h"
+#include "resample.h"
 #include "stages.h"
 
 namespace gsky {
@@ -285,18 +286,15 @@ __device__ __forceinline__ bool lin_coords(const RowRec &rr, const Leaf *__restr
 // NN gather of one window pixel in type T; returns false -> window fill.
 template <typename T>
 __device__ __forceinline__ bool nn_fetch(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
-  if (sx < 0 || sy < 0) return false;
-  const double ax = sx + 1.0e-10, ay = sy + 1.0e-10;
-  if (ax >= 2147483647.0 || ay >= 2147483647.0) return false;
-  const int ix = (int)ax, iy = (int)ay;
-  if (ix >= e.band_x || iy >= e.band_y) return false;
-  v = (typename VOf<T>::type)((const T *)e.band)[(long)iy * e.band_x + ix];
+  long idx;
+  if (!nn_index(sx, sy, e.band_x, e.band_y, idx)) return false;
+  v = (typename VOf<T>::type)((const T *)e.band)[idx];
   return true;
 }
 
-// One tap of a bilinear sample as a double.  A signed-byte band is a GDT_Byte
-// band to the warp kernel (PIXELTYPE=SIGNEDBYTE is metadata), so its taps
-// enter the sample -- and the nodata test -- as 0..255; gdal_copy_to(...,
+// One tap of a bilinear or cubic sample as a double.  A signed-byte band is a
+// GDT_Byte band to the warp kernel (PIXELTYPE=SIGNEDBYTE is metadata), so its
+// taps enter the sample -- and the nodata test -- as 0..255; gdal_copy_to(...,
 // GSKYHIP_SIGNEDBYTE) clamps the result to 0..255 and wraps it back
 // (warp.go:354-359).  Read as int8 the negative values all clamped to 0.
 template <typename T>
@@ -305,76 +303,26 @@ __device__ __forceinline__ double bil_tap(T v) {
   else return (double)v;
 }
 
+// bilinear_rule() / cubic_rule() (resample.h) of one window pixel in type T,
+// taps through the entry's typed band.  false -> window fill.
 template <typename T>
 __device__ __forceinline__ bool bil_fetch(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
-  int iSrcX = (int)floor(sx - 0.5);
-  int iSrcY = (int)floor(sy - 0.5);
-  double rX = 1.5 - (sx - iSrcX);
-  double rY = 1.5 - (sy - iSrcY);
-  if (iSrcX == -1) { iSrcX = 0; rX = 1; }
-  if (iSrcY == -1) { iSrcY = 0; rY = 1; }
-  double accR = 0.0, accDiv = 0.0;
   const T *band = (const T *)e.band;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int xx = iSrcX + (k & 1), yy = iSrcY + (k >> 1);
-    const double w = ((k & 1) ? (1.0 - rX) : rX) * ((k >> 1) ? (1.0 - rY) : rY);
-    if (xx < 0 || xx >= e.band_x || yy < 0 || yy >= e.band_y) continue;
-    const double d = bil_tap<T>(band[(long)yy * e.band_x + xx]);
-    if (e.has_nodata && (d == e.nodata64 || (e.nodata64 != e.nodata64 && d != d))) continue;
-    accDiv += w;
-    accR += d * w;
-  }
   double r;
-  if (accDiv == 1.0) r = accR;
-  else if (accDiv < 0.00001) return false;
-  else r = accR / accDiv;
-  if constexpr (std::is_same<T, float>::value) v = (float)r;
-  else v = gdal_copy_to(floor(r + 0.5), e.out_dtype).i;
+  if (!bilinear_rule(e.band_x, e.band_y, e.has_nodata, e.nodata64, sx, sy,
+                     [&](int xx, int yy) { return bil_tap<T>(band[(long)yy * e.band_x + xx]); }, r))
+    return false;
+  v = resample_store<T>(r, e.out_dtype);
   return true;
 }
-
-// One 1-D cubic convolution of GWKCubicResample4Sample (GDAL 3.0.1), every
-// operation in the written order (the numpy rule of tests/test_cubic.py
-// evaluates the same sequence).
-__device__ __forceinline__ double cubic_conv(double t, double f0, double f1, double f2, double f3) {
-  const double t2 = t * t;
-  const double t3 = t2 * t;
-  return f1 + 0.5 * (t * (f2 - f0) + t2 * (2.0 * f0 - 5.0 * f1 + 4.0 * f2 - f3) + t3 * (3.0 * (f1 - f2) + f3 - f0));
-}
-
-// The 4 x 4 taps of a cubic sample lie inside an nx x ny band (tested on the
-// floored coordinates as doubles: no integer conversion of a far coordinate).
-__device__ __forceinline__ bool cubic_inside(double fx, double fy, int nx, int ny) {
-  return fx >= 1.0 && fx + 2.0 < (double)nx && fy >= 1.0 && fy + 2.0 < (double)ny;
-}
-
-// GWKCubicResample4Sample of one window pixel in type T (GSKYHIP_RESAMPLE_CUBIC,
-// gskyhip.h): the 16 taps in fp64; a tap outside the band or equal to the
-// band's nodata hands the pixel to bil_fetch().  false -> window fill.
 template <typename T>
 __device__ __forceinline__ bool cub_fetch(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
-  const double fx = floor(sx - 0.5), fy = floor(sy - 0.5);
-  if (!cubic_inside(fx, fy, e.band_x, e.band_y)) return bil_fetch<T>(e, sx, sy, v);
-  const int iX = (int)fx, iY = (int)fy;
-  const double tx = sx - 0.5 - fx, ty = sy - 0.5 - fy;
-  const T *band = (const T *)e.band + ((long)(iY - 1) * e.band_x + (iX - 1));
-  double h[4];
-  bool anynd = false;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    double f[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      f[i] = bil_tap<T>(band[(long)j * e.band_x + i]);
-      anynd = anynd || (e.has_nodata && (f[i] == e.nodata64 || (e.nodata64 != e.nodata64 && f[i] != f[i])));
-    }
-    h[j] = cubic_conv(tx, f[0], f[1], f[2], f[3]);
-  }
-  if (anynd) return bil_fetch<T>(e, sx, sy, v);
-  const double r = cubic_conv(ty, h[0], h[1], h[2], h[3]);
-  if constexpr (std::is_same<T, float>::value) v = (float)r;
-  else v = gdal_copy_to(floor(r + 0.5), e.out_dtype).i;
+  const T *band = (const T *)e.band;
+  double r;
+  if (!cubic_rule(e.band_x, e.band_y, e.has_nodata, e.nodata64, sx, sy,
+                  [&](int xx, int yy) { return bil_tap<T>(band[(long)yy * e.band_x + xx]); }, r))
+    return false;
+  v = resample_store<T>(r, e.out_dtype);
   return true;
 }
 // cub_fetch() behind a call, for the generic kernels: inlined at each of a

@@ -22,13 +22,13 @@
 //     1e-7 of the data's scale (the resampling bar is 1e-4);
 //   * a cubic pixel with a nodata tap among the 16 takes the bilinear rule on
 //     the centre 2 x 2 of the taps it already holds (fp32 weights, dropped
-//     taps renormalised: render_bil_kernel's expressions);
+//     taps renormalised: bil4_renorm(), resample.h, as render_bil_kernel);
 //   * a pixel with a tap outside the band takes the bilinear rule with its
-//     edge cases (the -1 rule, taps outside dropped) through bil_sample()
-//     (render_lds.h, fp64) behind a branch: only the band's two outer rows
+//     edge cases (the -1 rule, taps outside dropped) through bilinear_rule()
+//     (resample.h, fp64) behind a branch: only the band's two outer rows
 //     and columns of source pixels reach it;
-//   * a band whose nodata no float32 equals runs cub_fetch() (render_common.h,
-//     fp64) one pixel at a time, for render_bil_kernel's reason: a sample
+//   * a band whose nodata no float32 equals runs cub_fetch() (cubic_rule(),
+//     resample.h, fp64) one pixel at a time, for render_bil_kernel's reason: a sample
 //     over taps that all hold (float)nodata must be exactly that value.
 #pragma once
 #include "render_bil.h"
@@ -194,23 +194,13 @@ __global__ __launch_bounds__(256, WPS) void render_cub_kernel(RenderArgs a, cons
             const float tv[4] = {__uint_as_float(tap[q][1].y), __uint_as_float(tap[q][1].z),
                                  __uint_as_float(tap[q][2].y), __uint_as_float(tap[q][2].z)};
             const float bwx[2] = {1.0f - tx[q], tx[q]}, bwy[2] = {1.0f - ty[q], ty[q]};
-            float aR = 0.0f, aD = 0.0f;
-#pragma unroll
-            for (int kk = 0; kk < 4; kk++) {
-              const float w = bwx[kk & 1] * bwy[kk >> 1];
-              const bool use = !(nd_nan ? (tv[kk] != tv[kk]) : (tv[kk] == ndf));
-              aD += use ? w : 0.0f;
-              aR += use ? tv[kk] * w : 0.0f;
-            }
-            v = fillv;
-            if (aD == 1.0f) v = aR;
-            else if (aD >= 0.00001f) v = aR / aD;
+            v = bil4_renorm<float>(tv, bwx, bwy, nd_nan, ndf, fillv);
           }
           if (!cub[q]) {   // a tap outside the band (or no sample at all): the bilinear rule, fp64
             double sx, sy;
             float got;
             v = fillv;
-            if (coords(h + q, sx, sy) && bil_sample<float>(bandp, bx, by, hnd, nd64, GSKYHIP_FLOAT32, sx, sy, got))
+            if (coords(h + q, sx, sy) && band_bil<float>(bandp, bx, by, hnd, nd64, GSKYHIP_FLOAT32, sx, sy, got))
               v = got;
           }
           fold(h + q, v);

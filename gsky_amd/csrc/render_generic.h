@@ -1,6 +1,7 @@
 // render_generic.h -- per-pixel sampling (descend/exact/approx coordinates,
-// GWKBilinear, typed loads) and the generic render kernels (any value type,
-// RGB or single namespace, auto-scale, complex tiles).  Included by render.hip
+// typed loads, the rules of resample.h over them) and the generic render
+// kernels (any value type, RGB or single namespace, auto-scale, complex
+// tiles).  Included by render.hip
 // (window / bytesRead kernels use the sampling helpers) and instantiated in
 // render_generic1.hip / render_generic3.hip so the NOUT=1 and NOUT=3 kernel
 // families compile as separate translation units.
@@ -45,78 +46,49 @@ __device__ __forceinline__ double load_dbl(const void *band, int src_dtype, long
   }
 }
 
-// GWKBilinearResample4Sample semantics (SURVEY 8a parity targets).
+// bilinear_rule() / cubic_rule() (resample.h) of a pair at (sx, sy): taps of
+// the pair's run-time source type through load_dbl(), the window fill where
+// the rule takes no sample.  Behind a call: the body is large and its callers'
+// loops are not.
 __device__ __noinline__ Val bilinear_value(const PairPlan &pp, double sx, double sy) {
-  int iSrcX = (int)floor(sx - 0.5);
-  int iSrcY = (int)floor(sy - 0.5);
-  double rX = 1.5 - (sx - iSrcX);
-  double rY = 1.5 - (sy - iSrcY);
-  if (iSrcX == -1) { iSrcX = 0; rX = 1; }
-  if (iSrcY == -1) { iSrcY = 0; rY = 1; }
-  double accR = 0.0, accDiv = 0.0;
-  const int xs4[4] = {iSrcX, iSrcX + 1, iSrcX, iSrcX + 1};
-  const int ys4[4] = {iSrcY, iSrcY, iSrcY + 1, iSrcY + 1};
-  const double w4[4] = {rX * rY, (1.0 - rX) * rY, rX * (1.0 - rY), (1.0 - rX) * (1.0 - rY)};
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    if (xs4[k] < 0 || xs4[k] >= pp.band_x || ys4[k] < 0 || ys4[k] >= pp.band_y) continue;
-    const double v = load_dbl(pp.band, pp.src_dtype, (long)ys4[k] * pp.band_x + xs4[k]);
-    if (pp.has_nodata && (v == pp.nodata || (pp.nodata != pp.nodata && v != v))) continue;
-    accDiv += w4[k];
-    accR += v * w4[k];
-  }
   double r;
-  if (accDiv == 1.0) r = accR;
-  else if (accDiv < 0.00001) return pp.fill;
-  else r = accR / accDiv;
-  if (pp.out_dtype == GSKYHIP_FLOAT32) { Val o; o.f = (float)r; return o; }
-  return gdal_copy_to(floor(r + 0.5), pp.out_dtype);
+  if (!bilinear_rule(pp.band_x, pp.band_y, pp.has_nodata, pp.nodata, sx, sy,
+                     [&](int xx, int yy) { return load_dbl(pp.band, pp.src_dtype, (long)yy * pp.band_x + xx); }, r))
+    return pp.fill;
+  return resample_store(r, pp.out_dtype);
 }
-
-// GWKCubicResample4Sample semantics (GSKYHIP_RESAMPLE_CUBIC, gskyhip.h): the
-// 4 x 4 taps around floor(s - 0.5), rows first, in fp64; bilinear_value()
-// where a tap lies outside the band or holds the band's nodata.
 __device__ __noinline__ Val cubic_value(const PairPlan &pp, double sx, double sy) {
-  const double fx = floor(sx - 0.5), fy = floor(sy - 0.5);
-  if (!cubic_inside(fx, fy, pp.band_x, pp.band_y)) return bilinear_value(pp, sx, sy);
-  const int iX = (int)fx, iY = (int)fy;
-  const double tx = sx - 0.5 - fx, ty = sy - 0.5 - fy;
-  const long base = (long)(iY - 1) * pp.band_x + (iX - 1);
-  double h[4];
-  bool anynd = false;
-  for (int j = 0; j < 4; j++) {
-    double f[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      f[i] = load_dbl(pp.band, pp.src_dtype, base + (long)j * pp.band_x + i);
-      anynd = anynd || (pp.has_nodata && (f[i] == pp.nodata || (pp.nodata != pp.nodata && f[i] != f[i])));
-    }
-    h[j] = cubic_conv(tx, f[0], f[1], f[2], f[3]);
-  }
-  if (anynd) return bilinear_value(pp, sx, sy);
-  const double r = cubic_conv(ty, h[0], h[1], h[2], h[3]);
-  if (pp.out_dtype == GSKYHIP_FLOAT32) { Val o; o.f = (float)r; return o; }
-  return gdal_copy_to(floor(r + 0.5), pp.out_dtype);
+  double r;
+  if (!cubic_rule(pp.band_x, pp.band_y, pp.has_nodata, pp.nodata, sx, sy,
+                  [&](int xx, int yy) { return load_dbl(pp.band, pp.src_dtype, (long)yy * pp.band_x + xx); }, r))
+    return pp.fill;
+  return resample_store(r, pp.out_dtype);
 }
 
-// Warped value of window pixel (i,row) of a pair: the source value or the
-// window's nodata fill (warp.go:246-247, 271-344).
+// Value of a pair's window at source coordinates (sx, sy) by rule RES: the
+// source value or the window's nodata fill (warp.go:271-344).
+template <int RES>
+__device__ __forceinline__ Val sampled_value(const PairPlan &pp, double sx, double sy) {
+  static_assert(RES == GSKYHIP_RESAMPLE_NEAREST || RES == GSKYHIP_RESAMPLE_BILINEAR || RES == GSKYHIP_RESAMPLE_CUBIC,
+                "a resampling rule of resample.h");
+  if (RES == GSKYHIP_RESAMPLE_BILINEAR) return bilinear_value(pp, sx, sy);
+  if (RES == GSKYHIP_RESAMPLE_CUBIC) return cubic_value(pp, sx, sy);
+  long idx;
+  if (!nn_index(sx, sy, pp.band_x, pp.band_y, idx)) return pp.fill;
+  Val v = load_val(pp.band, pp.src_dtype, idx);
+  if (pp.out_dtype == GSKYHIP_SIGNEDBYTE) v.i = (int32_t)(int8_t)(uint8_t)v.i;
+  return v;
+}
+
+// Warped value of window pixel (i,row) of a pair: sampled_value() at the
+// pixel's source coordinates, the window fill where the transform failed
+// (warp.go:246-247).
 template <bool GENERAL, int RES>
 __device__ __forceinline__ Val warped_value(const PairPlan &pp, const RowRec &rr, const Leaf *pool,
                                             const Xform *xf, int i, int row) {
   double sx, sy;
-  const bool ok = src_coords<GENERAL>(rr, pool, xf, pp.xoff, pp.yoff, pp.w, i, row, sx, sy);
-  if (!ok) return pp.fill;
-  if (RES == GSKYHIP_RESAMPLE_BILINEAR) return bilinear_value(pp, sx, sy);
-  if (RES == GSKYHIP_RESAMPLE_CUBIC) return cubic_value(pp, sx, sy);
-  if (sx < 0 || sy < 0) return pp.fill;
-  const double ax = sx + 1.0e-10, ay = sy + 1.0e-10;
-  if (ax >= 2147483647.0 || ay >= 2147483647.0) return pp.fill;
-  const int ix = (int)ax, iy = (int)ay;
-  if (ix >= pp.band_x || iy >= pp.band_y) return pp.fill;
-  Val v = load_val(pp.band, pp.src_dtype, (long)iy * pp.band_x + ix);
-  if (pp.out_dtype == GSKYHIP_SIGNEDBYTE) v.i = (int32_t)(int8_t)(uint8_t)v.i;
-  return v;
+  if (!src_coords<GENERAL>(rr, pool, xf, pp.xoff, pp.yoff, pp.w, i, row, sx, sy)) return pp.fill;
+  return sampled_value<RES>(pp, sx, sy);
 }
 
 // Mask bit for data pair `pp` at its window pixel (ic, ir): mask[iSrc] with
@@ -275,15 +247,13 @@ __device__ __forceinline__ void render_band(const RenderArgs &a, int t, int band
 
 // Branch-free NN sample of window pixel (sx, sy): the source value, or the
 // window fill when the pixel is outside the window or maps off the source
-// (warp.go:271-344).  One unconditional gather (index 0 when invalid).
+// (nn_index(), resample.h).  One unconditional gather (index 0 when invalid).
 template <typename T>
 __device__ __forceinline__ typename VOf<T>::type nn_px(const EntryD &e, double sx, double sy, bool in,
                                                        typename VOf<T>::type fillv) {
-  const double ax = sx + 1.0e-10, ay = sy + 1.0e-10;
-  const int ix = __double2int_rz(ax), iy = __double2int_rz(ay);
-  const bool ok = in && !(sx < 0) && !(sy < 0) && ax < 2147483647.0 && ay < 2147483647.0 && ix < e.band_x &&
-                  iy < e.band_y;
-  const long idx = ok ? (long)iy * e.band_x + ix : 0;
+  long at;
+  const bool ok = in && nn_index(sx, sy, e.band_x, e.band_y, at);
+  const long idx = ok ? at : 0;
   const typename VOf<T>::type raw = (typename VOf<T>::type)((const GPTR(T))e.band)[idx];
   return ok ? raw : fillv;
 }

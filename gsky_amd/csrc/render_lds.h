@@ -8,7 +8,8 @@
 // to render_nn_kernel (render_nn.h), bilinear float canvases to
 // render_bil_kernel (render_bil.h); what is left -- bilinear RGBA tiles,
 // bilinear integer canvases and bilinear stacks with a mask layer -- runs
-// render_lds_kernel below: wave w folds rows w, w+4, w+8, w+12 of the band,
+// render_lds_kernel below (per pixel bilinear_rule(), resample.h, in fp64):
+// wave w folds rows w, w+4, w+8, w+12 of the band,
 // each lane 8 consecutive pixels, over the band's entries listed in LDS
 // (kBandEnt per pass; a band with more parks its partial canvas in its own
 // output slot between passes).
@@ -86,34 +87,21 @@ __device__ __forceinline__ typename VOf<T>::type buf_load_w(__amdgpu_buffer_rsrc
   }
 }
 
-// GWKBilinearResample4Sample semantics of bil_fetch() (render_common.h), the
-// same fp64 expressions, for the band kernel: false -> window fill.
+// bilinear_rule() (resample.h) of one pixel of a band kernel in type T: the
+// taps are loads of the wave-uniform band in the global address space.
+// false -> window fill.  The rule and resample_store() stay together in this
+// function: with the conversion in the kernels' pixel loops the same code
+// held 2 to 6 more VGPRs (render_lds_kernel) or more scratch (render_bil_kernel).
 template <typename T>
-__device__ __forceinline__ bool bil_sample(const T *band, int bx, int by, bool has_nodata, double nodata64,
-                                           int out_dtype, double sx, double sy, typename VOf<T>::type &v) {
-  int iSrcX = (int)floor(sx - 0.5);
-  int iSrcY = (int)floor(sy - 0.5);
-  double rX = 1.5 - (sx - iSrcX);
-  double rY = 1.5 - (sy - iSrcY);
-  if (iSrcX == -1) { iSrcX = 0; rX = 1; }
-  if (iSrcY == -1) { iSrcY = 0; rY = 1; }
-  double accR = 0.0, accDiv = 0.0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    const int xx = iSrcX + (k & 1), yy = iSrcY + (k >> 1);
-    const double w = ((k & 1) ? (1.0 - rX) : rX) * ((k >> 1) ? (1.0 - rY) : rY);
-    if (xx < 0 || xx >= bx || yy < 0 || yy >= by) continue;
-    const double d = bil_tap<T>(((const GPTR(T))band)[(int64_t)yy * bx + xx]);
-    if (has_nodata && (d == nodata64 || (nodata64 != nodata64 && d != d))) continue;
-    accDiv += w;
-    accR += d * w;
-  }
+__device__ __forceinline__ bool band_bil(const T *band, int bx, int by, bool has_nodata, double nodata64,
+                                         int out_dtype, double sx, double sy, typename VOf<T>::type &v) {
   double r;
-  if (accDiv == 1.0) r = accR;
-  else if (accDiv < 0.00001) return false;
-  else r = accR / accDiv;
-  if constexpr (std::is_same<T, float>::value) v = (float)r;
-  else v = gdal_copy_to(floor(r + 0.5), out_dtype).i;
+  // a tap is inside the band: 0 <= yy and 0 < bx, the row offset is their unsigned product (one v_mad_u64_u32)
+  if (!bilinear_rule(bx, by, has_nodata, nodata64, sx, sy, [=](int xx, int yy) {
+        return bil_tap<T>(((const GPTR(T))band)[(int64_t)((uint64_t)(uint32_t)yy * (uint32_t)bx) + xx]);
+      }, r))
+    return false;
+  v = resample_store<T>(r, out_dtype);
   return true;
 }
 
@@ -259,7 +247,7 @@ __global__ __launch_bounds__(256) void render_lds_kernel(RenderArgs a, const Ent
             okc = lin_coords(R, pool, in ? ic : 0, sx, sy);
           }
           V v = fillv, got;
-          if (in && okc && bil_sample<T>(bandp, bx, by, hnd, nd64, odt, sx, sy, got)) v = got;
+          if (in && okc && band_bil<T>(bandp, bx, by, hnd, nd64, odt, sx, sy, got)) v = got;
           bool take = in && (v != nd);
           if (MASK && b.mask_pair >= 0) {
             if (take) take = !mask_fast<GSKYHIP_RESAMPLE_BILINEAR>(ents, rows, pool, a.mask, ents[pair], ic, ir);

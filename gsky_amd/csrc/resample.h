@@ -1,0 +1,157 @@
+// resample.h -- the per-pixel resampling rules, each written once: the
+// nearest-neighbour index rule (warp.go:271-300), GWKBilinearResample4Sample
+// and GWKCubicResample4Sample (GDAL 3.0.1) in fp64, the exit conversion to
+// the window's type, and the fp32 renormalised 2 x 2 of the float canvas
+// kernels.  The fp64 rules take a tap accessor `double tap(int xx, int yy)`,
+// called only for taps inside the band: what a kernel loads, and how (typed
+// pointer, global address space, run-time source type), stays with the kernel.
+// A new resampler is one more *_rule() here over the same accessor, one more
+// branch in the callers' wrappers (render_common.h, render_generic.h).
+#pragma once
+#include <type_traits>
+
+#include "gsky_device.h"
+
+namespace gsky {
+
+// A tap holds the band's nodata (a NaN nodata matches NaN taps).
+__device__ __forceinline__ bool tap_is_nodata(double v, bool has_nodata, double nodata64) {
+  return has_nodata && (v == nodata64 || (nodata64 != nodata64 && v != v));
+}
+
+// The nearest-neighbour index rule (warp.go:271-300): s < 0 -> no pixel,
+// + 1e-10, >= 2147483647 (or NaN) -> no pixel, truncation, >= n -> no pixel.
+constexpr double kNnEps = 1.0e-10;
+
+// The rule along one axis of n source pixels, branch-free (bytesRead tests x
+// alone, render.hip); i is meaningful only where the result is true.
+__device__ __forceinline__ bool nn_axis(double s, int n, int &i) {
+  const double a = s + kNnEps;
+  i = __double2int_rz(a);
+  return !(s < 0) && a < 2147483647.0 && i < n;
+}
+
+// The nearest-neighbour source pixel of (sx, sy) in a bx x by band; false ->
+// window fill (idx is then not to be used).
+__device__ __forceinline__ bool nn_index(double sx, double sy, int bx, int by, long &idx) {
+  if (sx < 0 || sy < 0) return false;
+  const double ax = sx + kNnEps, ay = sy + kNnEps;
+  if (!(ax < 2147483647.0) || !(ay < 2147483647.0)) return false;
+  const int ix = (int)ax, iy = (int)ay;
+  if (ix >= bx || iy >= by) return false;
+  idx = (long)iy * bx + ix;
+  return true;
+}
+
+// GWKBilinearResample4Sample up to and including the divide: the 2 x 2 taps
+// at floor(s - 0.5) with the -1 edge rule, taps outside the band or holding
+// its nodata dropped and the weights renormalised.  false -> no sample.
+// Every operation in the written order (-ffp-contract=off; the numpy rule of
+// tests/test_bilinear_edges.py evaluates the same sequence).
+template <typename Tap>
+__device__ __forceinline__ bool bilinear_rule(int bx, int by, bool has_nodata, double nodata64, double sx,
+                                              double sy, Tap tap, double &r) {
+  int iSrcX = (int)floor(sx - 0.5);
+  int iSrcY = (int)floor(sy - 0.5);
+  double rX = 1.5 - (sx - iSrcX);
+  double rY = 1.5 - (sy - iSrcY);
+  if (iSrcX == -1) { iSrcX = 0; rX = 1; }
+  if (iSrcY == -1) { iSrcY = 0; rY = 1; }
+  double accR = 0.0, accDiv = 0.0;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int xx = iSrcX + (k & 1), yy = iSrcY + (k >> 1);
+    const double w = ((k & 1) ? (1.0 - rX) : rX) * ((k >> 1) ? (1.0 - rY) : rY);
+    if (xx < 0 || xx >= bx || yy < 0 || yy >= by) continue;
+    const double d = tap(xx, yy);
+    // tap_is_nodata(), written out: as a call its short circuits are folded to
+    // selects before it is inlined, and render_lds_kernel then holds 4 more VGPRs
+    if (has_nodata && (d == nodata64 || (nodata64 != nodata64 && d != d))) continue;
+    accDiv += w;
+    accR += d * w;
+  }
+  if (accDiv == 1.0) r = accR;
+  else if (accDiv < 0.00001) return false;
+  else r = accR / accDiv;
+  return true;
+}
+
+// One 1-D cubic convolution of GWKCubicResample4Sample, every operation in
+// the written order (the numpy rule of tests/test_cubic.py evaluates the same
+// sequence).
+__device__ __forceinline__ double cubic_conv(double t, double f0, double f1, double f2, double f3) {
+  const double t2 = t * t;
+  const double t3 = t2 * t;
+  return f1 + 0.5 * (t * (f2 - f0) + t2 * (2.0 * f0 - 5.0 * f1 + 4.0 * f2 - f3) + t3 * (3.0 * (f1 - f2) + f3 - f0));
+}
+
+// The 4 x 4 taps of a cubic sample lie inside an nx x ny band (tested on the
+// floored coordinates as doubles: no integer conversion of a far coordinate).
+__device__ __forceinline__ bool cubic_inside(double fx, double fy, int nx, int ny) {
+  return fx >= 1.0 && fx + 2.0 < (double)nx && fy >= 1.0 && fy + 2.0 < (double)ny;
+}
+
+// GWKCubicResample4Sample (GSKYHIP_RESAMPLE_CUBIC, gskyhip.h): the 4 x 4 taps
+// around floor(s - 0.5), rows first; a tap outside the band or holding its
+// nodata hands the pixel to bilinear_rule().  false -> no sample.
+template <typename Tap>
+__device__ __forceinline__ bool cubic_rule(int bx, int by, bool has_nodata, double nodata64, double sx, double sy,
+                                           Tap tap, double &r) {
+  const double fx = floor(sx - 0.5), fy = floor(sy - 0.5);
+  if (!cubic_inside(fx, fy, bx, by)) return bilinear_rule(bx, by, has_nodata, nodata64, sx, sy, tap, r);
+  const int iX = (int)fx, iY = (int)fy;
+  const double tx = sx - 0.5 - fx, ty = sy - 0.5 - fy;
+  double h[4];
+  bool anynd = false;
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    double f[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      f[i] = tap(iX - 1 + i, iY - 1 + j);
+      anynd = anynd || tap_is_nodata(f[i], has_nodata, nodata64);
+    }
+    h[j] = cubic_conv(tx, f[0], f[1], f[2], f[3]);
+  }
+  if (anynd) return bilinear_rule(bx, by, has_nodata, nodata64, sx, sy, tap, r);
+  r = cubic_conv(ty, h[0], h[1], h[2], h[3]);
+  return true;
+}
+
+// The exit of a sample: (float)r into a float32 window, GDALCopyWords'
+// rounding and clamp of floor(r + 0.5) into an integer one.  T: the window's
+// element type (any integer T where only out_dtype tells the integer types
+// apart); the Val form picks by out_dtype at run time.
+template <typename T>
+__device__ __forceinline__ auto resample_store(double r, int out_dtype) {
+  if constexpr (std::is_same<T, float>::value) return (float)r;
+  else return gdal_copy_to(floor(r + 0.5), out_dtype).i;
+}
+__device__ __forceinline__ Val resample_store(double r, int out_dtype) {
+  Val o;
+  if (out_dtype == GSKYHIP_FLOAT32) o.f = resample_store<float>(r, out_dtype);
+  else o.i = resample_store<int32_t>(r, out_dtype);
+  return o;
+}
+
+// The float canvas kernels' 2 x 2 with nodata taps dropped (render_bil.h,
+// render_cub.h), weights and sums in WT: tv the taps x, x + 1 of the upper
+// row then of the lower, wx / wy the weights of (x, x + 1) and (y, y + 1).
+// All four taps are inside the band.  fillv where too little weight is left.
+template <typename WT>
+__device__ __forceinline__ float bil4_renorm(const float (&tv)[4], const WT (&wx)[2], const WT (&wy)[2], bool nd_nan,
+                                             float ndf, float fillv) {
+  WT aR = (WT)0.0, aD = (WT)0.0;
+#pragma unroll
+  for (int kk = 0; kk < 4; kk++) {
+    const WT w = wx[kk & 1] * wy[kk >> 1];
+    const bool use = !(nd_nan ? (tv[kk] != tv[kk]) : (tv[kk] == ndf));
+    aD += use ? w : (WT)0.0;
+    aR += use ? (WT)tv[kk] * w : (WT)0.0;
+  }
+  if (aD == (WT)1.0) return (float)aR;
+  if (aD >= (WT)0.00001) return (float)(aR / aD);
+  return fillv;
+}
+
+}  // namespace gsky

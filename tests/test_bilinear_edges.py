@@ -13,6 +13,10 @@ The paths, and the call that reaches each:
   (iv)  render_lds_kernel (render_lds.h)  integer granules: render(sp, pal, resample=1) for RGBA,
                                           render(..., rgba=False) for typed canvases
 
+The fp64 rule of (i), (iii), (iv) and of (ii)'s fp64 branch is one function,
+bilinear_rule() (resample.h); bilinear_value and bil_fetch wrap it with their
+own tap loads.  (ii)'s fp32 renormalisation is bil4_renorm() (resample.h).
+
 Part A needs no oracle: source and destination are both EPSG:3857, so neither
 side reprojects and the warp is the affine map of the two geotransforms.  They
 are built from powers of two, every source coordinate is exact in fp64, and

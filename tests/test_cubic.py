@@ -9,6 +9,10 @@ The paths, and the call that reaches each:
   (iii) the generic kernels (cub_fetch, render_common.h): batch.typed = False, and
         every integer type, RGBA, RGB, mask-layer and canvas=True call
 
+cubic_value and cub_fetch are wrappers: the fp64 rule itself is cubic_rule()
+(resample.h), with bilinear_rule() beside it for the fall-back; path (ii)
+takes both for its border pixels and bil4_renorm() for its nodata fall-back.
+
 Part A is the same-CRS geometry of test_bilinear_edges.py part A (EPSG:3857
 on both sides, power-of-two geotransforms, every source coordinate exact in
 fp64; `_rule` asserts it).  Part B reprojects EPSG:4326 -> EPSG:3857.
@@ -21,7 +25,8 @@ descending; an entry older than the canvas fills holes only), in `_merge`.
 
 Worst errors measured on an MI355X (every test prints its own; -s shows them):
 
-  (i)   warp_windows       0 ulp on every case (bit-equal to float32(rule)); integers: no difference
+  (i)   warp_windows       0 ulp on every case (bit-equal to float32(rule)); integers: no difference;
+                           A8 (Int32 / UInt32 / Float64 sources, bilinear and cubic) 0 ulp
   (ii)  render_cub_kernel  A1 (quadratic) 0; A2 noise 1.17e-7 * M (1:2; 1.15e-7 at 1:1, 1.14e-7 at 2:1);
                            A3 1.09e-7; A5 two entries 1.47e-7; A6 NaN nodata 1.85e-7, no nodata
                            1.04e-7, NaN data 1.23e-7
@@ -35,8 +40,8 @@ import pytest
 from gsky_amd import synth
 
 from .helpers import gpu_batch
-from .test_bilinear_edges import ND, PX, SRS, X0, Y0, _noise, _tile
-from .test_cubic_rule import cubic_rule, quadratic, to_type
+from .test_bilinear_edges import ND, PX, SRS, X0, Y0, _noise, _rule, _tile
+from .test_cubic_rule import _coords, cubic_rule, quadratic, to_type
 
 pytestmark = pytest.mark.gpu
 
@@ -446,6 +451,57 @@ def test_mask_layer(gpu):
         cv = _canvas(b.render(sp, resample=CUBIC, rgba=False), b, np.float32)
         assert b.status() == 0
         _check("(iii) mask", cv[0, :48, :64], val, sample, nd, big, worst, typed)
+    worst.show()
+
+
+@pytest.mark.parametrize("resample", [1, CUBIC], ids=["bilinear", "cubic"])
+def test_promoted_source_types(gpu, monkeypatch, resample):
+    """A8: Int32, UInt32 and Float64 bands, which the warp promotes to a
+    float32 window (warp.go:339-343): the only samples whose taps are not of
+    the window's type, read through load_dbl() by bilinear_value() and
+    cubic_value() (path (i), warp_windows(1) and (2)).  One 8 x 8 granule per
+    type with one nodata pixel off-centre on a 16 x 16 tile at 1:2: the rule
+    itself yields pixels of all four kinds -- 16 taps, the nodata fall-back,
+    the bilinear border, the -1 edge -- asserted before the GPU is asked.
+    Values span each type's range (float32 holds none of them exactly).
+    TileBatch has no name for a UInt32 tensor, so the test registers the
+    library's type code for its duration.  Bar: path (i)'s."""
+    import torch
+
+    from gsky_amd import _lib, tiles as tiles_mod
+    monkeypatch.setitem(tiles_mod.DTYPE_OF_TORCH, torch.uint32, _lib.UINT32)
+    rng = np.random.default_rng(38)
+    nd = 5.0
+    datas = [rng.integers(-2 ** 31, 2 ** 31 - 1, (8, 8)).astype(np.int32),
+             rng.integers(0, 2 ** 32 - 1, (8, 8)).astype(np.uint32), rng.uniform(-1000.0, 1000.0, (8, 8))]
+    for d in datas:
+        d[2, 5] = nd
+    granules = [_gran(d, 2.0, 0.0, 0.0, nd, poly="P%d" % k) for k, d in enumerate(datas)]
+    tile = _tile(16, 16)
+    worst = _Worst("A8 promoted types, resample %d" % resample)
+    refs = []
+    for g in granules:
+        sample, has, cub, win = cubic_rule(g.data, nd, g.geot, tile)
+        sx, sy = _coords(g, tile)
+        fx, fy = np.floor(sx - 0.5), np.floor(sy - 0.5)
+        inside = ((fy >= 1) & (fy + 2 < 8))[:, None] & ((fx >= 1) & (fx + 2 < 8))[None, :]
+        edge = (fy == -1)[:, None] | (fx == -1)[None, :]
+        assert win == [0, 0, 16, 16] and has.all()
+        assert cub.any() and (inside & ~cub).any() and (~inside & ~edge).any() and edge.any()
+        if resample == 1:
+            sample, has, _, win = _rule(g.data, nd, g.geot, tile)
+        refs.append((np.where(has, sample.astype(np.float32), np.float32(nd)), sample))
+        assert (refs[-1][0].astype(np.float64) != sample).any()   # the promotion rounds
+    cfg = synth.SynthConfig("A8", granules, SRS, [tile] * 3, [[0], [1], [2]], [""], (0.0, 1.0, 0.0, 0), None,
+                            resample=resample)
+    wins = gpu_batch(cfg).warp_windows(resample)
+    assert len(wins) == 3
+    for k, (arr, bbox, tname, wnd) in enumerate(wins):
+        val, sample = refs[k]
+        assert tname == "Float32" and wnd == nd and bbox == [0, 0, 16, 16], (k, tname, wnd, bbox)
+        big = float(np.abs(datas[k].astype(np.float64)).max())
+        n = _check("(i)", arr.cpu().numpy(), val, sample, np.float32(nd), big, worst, (resample, datas[k].dtype))
+        assert n == 256
     worst.show()
 
 
