@@ -367,10 +367,11 @@ __device__ void huff_lengths(const uint32_t *freq, int n, int maxbits, uint8_t *
     for (int i = root - 1; i >= 0; i--) {
       const int d = H.depth[H.parent[i]] + 1;
       H.depth[i] = (uint8_t)min(d, 255);
-      if (i < m) {
-        if (d > maxbits) overflow++;
-        bl_count[min(d, maxbits)]++;
-      }
+      // every node past maxbits counts, internal ones too (as in zlib, where a
+      // clamped parent clamps its children): k leaves under a node at maxbits
+      // come with k - 2 internal nodes and need (2k - 2) / 2 = k - 1 moves
+      if (d > maxbits) overflow++;
+      if (i < m) bl_count[min(d, maxbits)]++;
     }
     while (overflow > 0) {   // zlib gen_bitlen: move leaves until the code fits
       int bits = maxbits - 1;
