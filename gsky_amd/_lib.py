@@ -24,6 +24,7 @@ CRS_LONGLAT, CRS_WEBMERC, CRS_AEA, CRS_SINU = 0, 1, 2, 3
 CRS_TMERC, CRS_LCC, CRS_STERE_POLAR, CRS_GEOS, CRS_LAEA, CRS_CEA, CRS_MERC = 4, 5, 6, 7, 8, 9, 10
 RESAMPLE_NEAREST, RESAMPLE_BILINEAR = 0, 1
 RESAMPLE_CUBIC = 2
+RESAMPLE_AVERAGE, RESAMPLE_MODE = 3, 4   # the area rules (include/gskyhip.h)
 # value-type hint bits of gskyhip_render_tiles_typed
 VT_BIT = {BYTE: 1, SIGNEDBYTE: 2, INT16: 4, UINT16: 8, FLOAT32: 16}
 MAX_OVR = 12

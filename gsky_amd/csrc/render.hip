@@ -2149,9 +2149,7 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
                   const uint8_t *ramp, uint8_t *rgba_out, void *canvas_out, int phase) {
   if (n_out != 1 && n_out != 3) return GSKYHIP_E_ARG;  // ogc_encoders.go:135-136
   for (int k = 0; k < n_out; k++) if (out_ns[k] < 0 || out_ns[k] >= 4) return GSKYHIP_E_ARG;
-  if (rc.resample != GSKYHIP_RESAMPLE_NEAREST && rc.resample != GSKYHIP_RESAMPLE_BILINEAR &&
-      rc.resample != GSKYHIP_RESAMPLE_CUBIC)
-    return GSKYHIP_E_ARG;
+  if (rc.resample < GSKYHIP_RESAMPLE_NEAREST || rc.resample > GSKYHIP_RESAMPLE_MODE) return GSKYHIP_E_ARG;
   // rgba_out == NULL: canvases only (WCS GetCoverage, FusionUnscale, ows.go:728)
   const bool autom = rgba_out && sp.offset == 0.0 && sp.scale == 0.0 && sp.clip == 0.0;
   if ((autom || !rgba_out) && !canvas_out) return GSKYHIP_E_ARG;
@@ -2205,6 +2203,11 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
     // cubic: float32 canvases without a mask layer have a band kernel
     // (render_cub_kernel); every other combination runs the generic kernels
     if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask) lds_mode = kCanvas | kCubic;
+  } else if (rc.resample == GSKYHIP_RESAMPLE_AVERAGE) {
+    // average: the same combination has render_avg_kernel (render_area.h)
+    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask) lds_mode = kCanvas | kAverage;
+  } else if (rc.resample == GSKYHIP_RESAMPLE_MODE) {
+    // mode: the generic kernels
   } else if (vt && n_out == 1 && !autom) {
     if (a.write_rgba && !canvas_out) lds_mode = bil ? kBilinear : 0;
     else if (!rgba_out && canvas_out) lds_mode = kCanvas | (bil ? kBilinear : 0);
@@ -2347,6 +2350,12 @@ int launch_warp_windows(const RenderCall &rc, int32_t *bbox_out, int32_t *dtype_
                        cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
   else if (rc.resample == GSKYHIP_RESAMPLE_CUBIC)
     hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_CUBIC>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
+                       cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
+  else if (rc.resample == GSKYHIP_RESAMPLE_AVERAGE)
+    hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_AVERAGE>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
+                       cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
+  else if (rc.resample == GSKYHIP_RESAMPLE_MODE)
+    hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_MODE>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
                        cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
   else
     hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_NEAREST>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,

@@ -207,7 +207,7 @@ struct RenderArgs {
   MinMax *minmax;        // n_tiles * 3
   int write_rgba;
   const EntryD *entries;
-  int lds_mode;          // typed band kernels: kBilinear | kCanvas | kCubic bits of the call
+  int lds_mode;          // typed band kernels: kBilinear | kCanvas | kCubic | kAverage bits of the call
   const int64_t *cov_offsets;  // canvas mode: per tile element offset into one image (NULL: slots)
   int64_t cov_stride;          // ... and that image's row stride (elements)
 };
@@ -332,6 +332,34 @@ __device__ __noinline__ bool cub_fetch_call(const EntryD &e, double sx, double s
   return cub_fetch<T>(e, sx, sy, v);
 }
 
+// average_rule() / mode_rule() (resample.h; RES picks) of window pixel (ic, ir)
+// of a simple tile's entry, whose source coordinate is (sx, sy): the footprint
+// from the neighbours' lin_coords() inside the entry's window (gskyhip.h, step
+// 1; the row records of the window's rows lie beside each other), taps
+// through the entry's typed band.  Returns the sample, or fillv where the rule
+// takes none.  Behind a call, as cub_fetch_call(); the value comes back in a
+// register (a reference argument of a call lives in scratch).
+template <typename T, int RES>
+__device__ __noinline__ typename VOf<T>::type area_fetch(const EntryD &e, const RowRec *__restrict__ rows,
+                                                         const Leaf *__restrict__ pool, int ic, int ir, double sx,
+                                                         double sy, typename VOf<T>::type fillv) {
+  const RowRec *rr = rows + e.row_base + ir;
+  double ux = 0.0, uy = 0.0, vx = 0.0, vy = 0.0, nx, ny;
+  if (ic + 1 < e.w && lin_coords(*rr, pool, ic + 1, nx, ny)) { ux = nx - sx; uy = ny - sy; }
+  else if (ic > 0 && lin_coords(*rr, pool, ic - 1, nx, ny)) { ux = sx - nx; uy = sy - ny; }
+  if (ir + 1 < e.h && lin_coords(rr[1], pool, ic, nx, ny)) { vx = nx - sx; vy = ny - sy; }
+  else if (ir > 0 && lin_coords(rr[-1], pool, ic, nx, ny)) { vx = sx - nx; vy = sy - ny; }
+  const double hx = area_half(ux, vx), hy = area_half(uy, vy);
+  const T *band = (const T *)e.band;
+  auto tap = [&](int xx, int yy) { return bil_tap<T>(band[(long)yy * e.band_x + xx]); };
+  double r;
+  const bool ok = RES == GSKYHIP_RESAMPLE_MODE
+                      ? mode_rule(e.band_x, e.band_y, e.has_nodata, e.nodata64, sx, sy, hx, hy, tap, r)
+                      : average_rule(e.band_x, e.band_y, e.has_nodata, e.nodata64, sx, sy, hx, hy, tap, r);
+  if (!ok) return fillv;
+  return resample_store<T>(r, e.out_dtype);
+}
+
 // Full per-pixel path (exact points, descend): only complex tiles and the
 // drop-in window kernel run it.
 __device__ __noinline__ bool descend_coords(const Xform &t, int xoff, double yrow, int n0, const double *v,
@@ -438,7 +466,7 @@ __device__ __forceinline__ bool mask_fast_pair(const EntryD *__restrict__ ents, 
   int32_t v = 0;
   bool ok = false;
   if (!lin_coords(rows[m.row_base + my], pool, mx, sx, sy)) {   // failed transform -> fill
-  } else if (RES == GSKYHIP_RESAMPLE_CUBIC) {   // the mask raster warps by the data's rule
+  } else if (mask_res(RES) == GSKYHIP_RESAMPLE_CUBIC) {   // the mask raster warps by the data's rule (mask_res())
     switch (m.out_dtype) {
       case GSKYHIP_BYTE: ok = cub_fetch_call<uint8_t>(m, sx, sy, v); break;
       case GSKYHIP_SIGNEDBYTE: ok = cub_fetch_call<int8_t>(m, sx, sy, v); break;
@@ -468,6 +496,7 @@ __device__ __forceinline__ bool mask_fast(const EntryD *__restrict__ ents, const
 constexpr int kLdsBandRows = 16;   // rows per block of render_lds_kernel
 constexpr int kBilinear = 4, kCanvas = 8;   // render_lds_kernel modes (RenderArgs.lds_mode)
 constexpr int kCubic = 16;                  // float32 canvases by cubic convolution: render_cub_kernel (render_cub.h)
+constexpr int kAverage = 32;                // float32 canvases by area average: render_avg_kernel (render_area.h)
 
 // The typed band kernels (render_lds.hip) for value type `vt`.
 void launch_band_kernels(const RenderArgs &a, int vt, bool mask, int n_items, hipStream_t s);

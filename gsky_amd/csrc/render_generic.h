@@ -65,6 +65,45 @@ __device__ __noinline__ Val cubic_value(const PairPlan &pp, double sx, double sy
   return resample_store(r, pp.out_dtype);
 }
 
+// average_rule() / mode_rule() (resample.h) of a pair over the footprint
+// (sx +- hx, sy +- hy), taps as above.
+__device__ __noinline__ Val average_value(const PairPlan &pp, double sx, double sy, double hx, double hy) {
+  double r;
+  if (!average_rule(pp.band_x, pp.band_y, pp.has_nodata, pp.nodata, sx, sy, hx, hy,
+                    [&](int xx, int yy) { return load_dbl(pp.band, pp.src_dtype, (long)yy * pp.band_x + xx); }, r))
+    return pp.fill;
+  return resample_store(r, pp.out_dtype);
+}
+__device__ __noinline__ Val mode_value(const PairPlan &pp, double sx, double sy, double hx, double hy) {
+  double r;
+  if (!mode_rule(pp.band_x, pp.band_y, pp.has_nodata, pp.nodata, sx, sy, hx, hy,
+                 [&](int xx, int yy) { return load_dbl(pp.band, pp.src_dtype, (long)yy * pp.band_x + xx); }, r))
+    return pp.fill;
+  return resample_store(r, pp.out_dtype);
+}
+
+// Half extents of the footprint of window pixel (i, row), whose source
+// coordinate is (sx, sy) (gskyhip.h, step 1): u from the next pixel of the
+// row, else the previous one, else zero; v the same along rows, whose records
+// lie beside rr; neighbours inside the pair's window only.
+template <bool GENERAL>
+__device__ __noinline__ void area_footprint(const PairPlan &pp, const RowRec &rr, const Leaf *pool, const Xform *xf,
+                                            int i, int row, double sx, double sy, double &hx, double &hy) {
+  double ux = 0.0, uy = 0.0, vx = 0.0, vy = 0.0, nx, ny;
+  if (i + 1 < pp.w && src_coords<GENERAL>(rr, pool, xf, pp.xoff, pp.yoff, pp.w, i + 1, row, nx, ny)) {
+    ux = nx - sx; uy = ny - sy;
+  } else if (i > 0 && src_coords<GENERAL>(rr, pool, xf, pp.xoff, pp.yoff, pp.w, i - 1, row, nx, ny)) {
+    ux = sx - nx; uy = sy - ny;
+  }
+  if (row + 1 < pp.h && src_coords<GENERAL>((&rr)[1], pool, xf, pp.xoff, pp.yoff, pp.w, i, row + 1, nx, ny)) {
+    vx = nx - sx; vy = ny - sy;
+  } else if (row > 0 && src_coords<GENERAL>((&rr)[-1], pool, xf, pp.xoff, pp.yoff, pp.w, i, row - 1, nx, ny)) {
+    vx = sx - nx; vy = sy - ny;
+  }
+  hx = area_half(ux, vx);
+  hy = area_half(uy, vy);
+}
+
 // Value of a pair's window at source coordinates (sx, sy) by rule RES: the
 // source value or the window's nodata fill (warp.go:271-344).
 template <int RES>
@@ -88,7 +127,13 @@ __device__ __forceinline__ Val warped_value(const PairPlan &pp, const RowRec &rr
                                             const Xform *xf, int i, int row) {
   double sx, sy;
   if (!src_coords<GENERAL>(rr, pool, xf, pp.xoff, pp.yoff, pp.w, i, row, sx, sy)) return pp.fill;
-  return sampled_value<RES>(pp, sx, sy);
+  if constexpr (is_area(RES)) {   // the area rules need the pixel's footprint, from its neighbours
+    double hx, hy;
+    area_footprint<GENERAL>(pp, rr, pool, xf, i, row, sx, sy, hx, hy);
+    return RES == GSKYHIP_RESAMPLE_AVERAGE ? average_value(pp, sx, sy, hx, hy) : mode_value(pp, sx, sy, hx, hy);
+  } else {
+    return sampled_value<RES>(pp, sx, sy);
+  }
 }
 
 // Mask bit for data pair `pp` at its window pixel (ic, ir): mask[iSrc] with
@@ -104,7 +149,7 @@ __device__ __forceinline__ bool mask_at(const RenderArgs &a, const PairPlan &pp,
   const int slot = mask_slot(mq.out_dtype);
   if (slot < 0) return false;    // flagged in plan_tiles (not a bit-mask type)
   const RowRec &mr = a.rows[(long)mp * a.max_h + my];
-  Val v = warped_value<GENERAL, RES>(mq, mr, a.pool, a.xforms + mp, mx, my);
+  Val v = warped_value<GENERAL, mask_res(RES)>(mq, mr, a.pool, a.xforms + mp, mx, my);
   return mask_bit(a.mask[slot], mq.out_dtype, v.i);
 }
 
@@ -344,6 +389,9 @@ __device__ __forceinline__ void render_fast_t(const RenderArgs &a, const EntryD 
             v = fillv;
             V got;
             if (in && okq[q] && cub_fetch_call<T>(e, sx, sy, got)) v = got;
+          } else if constexpr (is_area(RES)) {
+            v = fillv;
+            if (in && okq[q]) v = area_fetch<T, RES>(e, rows, pool, ic, ir, sx, sy, fillv);
           } else {
             v = nn_px<T>(e, sx, sy, in && okq[q], fillv);
           }
@@ -485,6 +533,12 @@ static void dispatch_render_t(const RenderArgs &a, int resample, bool mask, dim3
   } else if (resample == GSKYHIP_RESAMPLE_CUBIC) {
     if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBIC, true>(a, grid, general_only, s);
     else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBIC, false>(a, grid, general_only, s);
+  } else if (resample == GSKYHIP_RESAMPLE_AVERAGE) {
+    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_AVERAGE, true>(a, grid, general_only, s);
+    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_AVERAGE, false>(a, grid, general_only, s);
+  } else if (resample == GSKYHIP_RESAMPLE_MODE) {
+    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_MODE, true>(a, grid, general_only, s);
+    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_MODE, false>(a, grid, general_only, s);
   } else {
     if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_NEAREST, true>(a, grid, general_only, s);
     else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_NEAREST, false>(a, grid, general_only, s);

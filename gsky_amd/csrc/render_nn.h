@@ -929,14 +929,21 @@ void launch_nn_t(const RenderArgs &a, bool mask, hipStream_t s) {
 void launch_bil(const RenderArgs &a, int n_items, hipStream_t s);   // render_bil.h, band_f32.hip
 void launch_cub(const RenderArgs &a, hipStream_t s);                // render_cub.h, band_f32.hip
 
-// Band kernel of one call: cubic float canvases -> render_cub_kernel
-// (launch_render sets kCubic for float32 canvases without a mask layer only);
+void launch_avg(const RenderArgs &a, hipStream_t s);                // render_area.h, band_f32.hip
+
+// Band kernel of one call: cubic float canvases -> render_cub_kernel, area
+// average float canvases -> render_avg_kernel (launch_render sets kCubic and
+// kAverage for float32 canvases without a mask layer only);
 // bilinear float canvases without a mask layer -> render_bil_kernel; other
 // bilinear work -> render_lds_kernel; nearest neighbour -> render_nn_kernel.
 template <typename T>
 void launch_band_t(const RenderArgs &a, bool mask, int n_items, hipStream_t s) {
   if ((a.lds_mode & kCubic) != 0) {
     if constexpr (std::is_same<T, float>::value) launch_cub(a, s);
+    return;
+  }
+  if ((a.lds_mode & kAverage) != 0) {
+    if constexpr (std::is_same<T, float>::value) launch_avg(a, s);
     return;
   }
   if ((a.lds_mode & kBilinear) != 0) {

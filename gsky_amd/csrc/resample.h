@@ -1,6 +1,7 @@
 // resample.h -- the per-pixel resampling rules, each written once: the
 // nearest-neighbour index rule (warp.go:271-300), GWKBilinearResample4Sample
-// and GWKCubicResample4Sample (GDAL 3.0.1) in fp64, the exit conversion to
+// and GWKCubicResample4Sample (GDAL 3.0.1) in fp64, the area average and mode
+// over a pixel's footprint (after GWKAverageOrMode), the exit conversion to
 // the window's type, and the fp32 renormalised 2 x 2 of the float canvas
 // kernels.  The fp64 rules take a tap accessor `double tap(int xx, int yy)`,
 // called only for taps inside the band: what a kernel loads, and how (typed
@@ -116,6 +117,112 @@ __device__ __forceinline__ bool cubic_rule(int bx, int by, bool has_nodata, doub
   if (anynd) return bilinear_rule(bx, by, has_nodata, nodata64, sx, sy, tap, r);
   r = cubic_conv(ty, h[0], h[1], h[2], h[3]);
   return true;
+}
+
+// ---------------------------------------------------------------- area rules
+// GSKYHIP_RESAMPLE_AVERAGE / _MODE (gskyhip.h), after GDAL's GWKAverageOrMode:
+// a pixel's footprint in the source is the box [sx - hx, sx + hx] x [sy - hy,
+// sy + hy] (hx, hy >= 0.5 from the pixel's neighbours: area_half(); the
+// callers' wrappers take the neighbours' coordinates), its taps the outer
+// product of area_taps() along x and y, rows outer.
+constexpr int kAreaTaps = 8;   // taps per axis at the most (64 per pixel)
+
+constexpr bool is_area(int res) { return res == GSKYHIP_RESAMPLE_AVERAGE || res == GSKYHIP_RESAMPLE_MODE; }
+// The rule a raster of the mask layer warps by under the data's rule `res`:
+// nearest neighbour under the area rules (bit fields are neither averaged nor
+// voted), else the data's.
+constexpr int mask_res(int res) { return is_area(res) ? GSKYHIP_RESAMPLE_NEAREST : res; }
+
+// Half extent of a footprint along one axis from that axis' component of
+// u = S(i + 1, row) - S(i, row) and v = S(i, row + 1) - S(i, row).
+__device__ __forceinline__ double area_half(double u, double v) { return fmax(0.5, 0.5 * (fabs(u) + fabs(v))); }
+
+// The taps of [s - h, s + h] along an axis of n source pixels: lo, lo +
+// stride, ... < hi, at most kAreaTaps of them; false -> none.  The bounds are
+// compared as doubles (cubic_inside()'s reason); [x0, x1] is the interval.
+struct AreaAxis {
+  int lo, hi, stride;
+  double x0, x1;
+  __device__ __forceinline__ int count() const { return (hi - lo + stride - 1) / stride; }
+  // covered length of tap xx; 1 once the taps are strided
+  __device__ __forceinline__ double weight(int xx) const {
+    return stride == 1 ? fmin((double)xx + 1.0, x1) - fmax((double)xx, x0) : 1.0;
+  }
+};
+__device__ __forceinline__ bool area_taps(double s, double h, int n, AreaAxis &a) {
+  a.x0 = s - h;
+  a.x1 = s + h;
+  if (!(fabs(a.x0) < INFINITY) || !(fabs(a.x1) < INFINITY)) return false;
+  const double lo = fmax(floor(a.x0), 0.0), hi = fmin(ceil(a.x1), (double)n);
+  if (hi <= lo) return false;
+  a.lo = (int)lo;
+  a.hi = (int)hi;
+  a.stride = (a.hi - a.lo + kAreaTaps - 1) / kAreaTaps;
+  return true;
+}
+
+// AVERAGE: the weighted mean of the taps that do not hold the band's nodata,
+// w = wx * wy, accW += w and accR += d * w in scan order.  false -> no sample.
+// With hx = hy = 0.5 the taps and weights are bilinear_rule()'s.
+template <typename Tap>
+__device__ __forceinline__ bool average_rule(int bx, int by, bool has_nodata, double nodata64, double sx, double sy,
+                                             double hx, double hy, Tap tap, double &r) {
+  AreaAxis ax, ay;
+  if (!area_taps(sx, hx, bx, ax) || !area_taps(sy, hy, by, ay)) return false;
+  double accR = 0.0, accW = 0.0;
+  for (int yy = ay.lo; yy < ay.hi; yy += ay.stride) {
+    const double wy = ay.weight(yy);
+    for (int xx = ax.lo; xx < ax.hi; xx += ax.stride) {
+      const double w = ax.weight(xx) * wy;
+      const double d = tap(xx, yy);
+      if (tap_is_nodata(d, has_nodata, nodata64) || !(w > 0.0)) continue;
+      accW += w;
+      accR += d * w;
+    }
+  }
+  if (accW < 0.00001) return false;
+  r = accR / accW;
+  return true;
+}
+
+// MODE: taps of equal value form a class (a NaN tap that is not nodata is a
+// class of its own), a class weighs the sum of its taps' w in scan order, the
+// sample is the value of the heaviest class, the first in scan order among
+// equals.  No tap storage: a tap whose value an earlier tap holds is skipped,
+// any other sums its class over the taps after it.  false -> no sample.
+template <typename Tap>
+__device__ __forceinline__ bool mode_rule(int bx, int by, bool has_nodata, double nodata64, double sx, double sy,
+                                          double hx, double hy, Tap tap, double &r) {
+  AreaAxis ax, ay;
+  if (!area_taps(sx, hx, bx, ax) || !area_taps(sy, hy, by, ay)) return false;
+  const int nx = ax.count(), n = nx * ay.count();
+  // tap k of the scan: its value, and its weight (0: dropped)
+  auto at = [&](int k, double &d) {
+    const int xx = ax.lo + (k % nx) * ax.stride, yy = ay.lo + (k / nx) * ay.stride;
+    d = tap(xx, yy);
+    const double w = ax.weight(xx) * ay.weight(yy);
+    return (tap_is_nodata(d, has_nodata, nodata64) || !(w > 0.0)) ? 0.0 : w;
+  };
+  bool found = false;
+  double best = 0.0;
+  for (int k = 0; k < n; k++) {
+    double d, o;
+    double cw = at(k, d);
+    if (cw == 0.0) continue;
+    bool seen = false;
+    for (int j = 0; j < k && !seen; j++) seen = at(j, o) != 0.0 && o == d;
+    if (seen) continue;
+    for (int j = k + 1; j < n; j++) {
+      const double w = at(j, o);
+      if (w != 0.0 && o == d) cw += w;
+    }
+    if (!found || cw > best) {
+      found = true;
+      best = cw;
+      r = d;
+    }
+  }
+  return found;
 }
 
 // The exit of a sample: (float)r into a float32 window, GDALCopyWords'

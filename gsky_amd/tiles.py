@@ -213,8 +213,10 @@ class TileBatch:
         """Warp + merge + scale + RGBA for every tile.  Returns the RGBA
         tensor (n_tiles, H, W, 4); with canvas=True also the typed canvases
         (n_tiles, n_out, H*W*4 bytes).  rgba=False renders canvases only (WCS).
-        resample: 0 nearest, 1 bilinear, 2 cubic convolution
-        (_lib.RESAMPLE_*; GDAL's 4-sample formulas, include/gskyhip.h).
+        resample: 0 nearest, 1 bilinear, 2 cubic convolution, 3 area average,
+        4 area mode (_lib.RESAMPLE_*; GDAL's 4-sample formulas and the area
+        rules modelled on GWKAverageOrMode, include/gskyhip.h).  Under 3 and 4
+        rasters of the mask layer warp by nearest neighbour.
         phase 1 / 2 run the planning / render kernels alone (same arguments)."""
         n_out = len(self.namespaces)
         if n_out not in (1, 3):
@@ -291,7 +293,7 @@ class TileBatch:
 
     def graph(self, params: ScaleParams, palette: Optional[Palette] = None, resample: int = 0) -> "RenderGraph":
         """The batch's render (planning + band kernels, RGBA out) captured as
-        one HIP graph (see RenderGraph)."""
+        one HIP graph (see RenderGraph).  resample: as render(), 0..4."""
         return RenderGraph(self, params, palette, resample)
 
     def render_coverage(self, params: ScaleParams, out: torch.Tensor, offsets, resample: int = 0,
@@ -300,8 +302,9 @@ class TileBatch:
         written straight into `out` (a 2-D tensor of the canvas type) with
         tile t's top-left at flat element offset offsets[t]
         (gskyhip_render_coverage; no per-tile slots, no assembly copy).
-        resample: 0 nearest, 1 bilinear, 2 cubic convolution; float32
-        coverages have a band kernel for each."""
+        resample: 0 nearest, 1 bilinear, 2 cubic convolution, 3 area average,
+        4 area mode; float32 coverages have a band kernel for 0..3, mode
+        runs the generic kernels."""
         if out.dim() != 2:
             raise ValueError("coverage must be 2-D")
         offs = offsets if isinstance(offsets, torch.Tensor) else torch.tensor(list(offsets), dtype=torch.int64)
@@ -366,7 +369,8 @@ class TileBatch:
     def warp_windows(self, resample: int = 0):
         """The FlexRasters of tile_grpc.go:228-241: per pair
         (window tensor, bbox [xoff, yoff, w, h], type name, nodata).
-        resample: 0 nearest, 1 bilinear, 2 cubic convolution."""
+        resample: 0 nearest, 1 bilinear, 2 cubic convolution, 3 area average,
+        4 area mode."""
         npairs = self.n_pairs
         bbox = torch.zeros((max(1, npairs), 4), dtype=torch.int32, device=self.device)
         dt = torch.zeros(max(1, npairs), dtype=torch.int32, device=self.device)

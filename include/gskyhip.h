@@ -344,6 +344,47 @@ int64_t gskyhip_render_workspace_size(int n_tiles, int n_pairs, int max_tile_hei
  * value.  Accepted by gskyhip_render_tiles / _phase / _typed,
  * gskyhip_render_coverage and gskyhip_warp_windows. */
 #define GSKYHIP_RESAMPLE_CUBIC 2
+/* Area resampling, for destination pixels that cover more than one source
+ * pixel; modelled on GDAL's GWKAverageOrMode (-r average, -r mode) and, like
+ * bilinear and cubic, not pinned against it.  S(i, row) = (sx, sy) is the
+ * source coordinate of window pixel (i, row) of a pair (pixel centres at
+ * +0.5), whatever kind of row yields it.
+ *  1. Footprint.  u = S(i + 1, row) - S(i, row); where i + 1 is outside the
+ *     window [0, w) x [0, h) or that transform fails, u = S(i, row) - S(i - 1,
+ *     row); where neither neighbour exists or succeeds, u = (0, 0).  v is the
+ *     same along rows.  hx = max(0.5, 0.5 (|u.x| + |v.x|)), hy = max(0.5,
+ *     0.5 (|u.y| + |v.y|)); the footprint is [sx - hx, sx + hx] x [sy - hy,
+ *     sy + hy], the bounding box of the linearised pixel and never less than
+ *     one source pixel wide.  A failed centre transform gives the window fill.
+ *  2. Taps along an axis of n source pixels, for [x0, x1] = [s - h, s + h]: a
+ *     non-finite bound means none; lo = max(floor(x0), 0), hi = min(ceil(x1),
+ *     n), compared as doubles; hi <= lo means none; else stride = (hi - lo +
+ *     7) / 8 (integers) and the taps are lo, lo + stride, ... < hi: at most 8
+ *     per axis, 64 per pixel.  With stride 1 a tap xx weighs its covered
+ *     length min(xx + 1, x1) - max(xx, x0), with a larger stride every tap
+ *     weighs 1.
+ *  3. A pixel's taps are the outer product of the two axes in scan order, rows
+ *     outer, w = wx * wy; a tap equal to the band's nodata (a NaN nodata
+ *     matches NaN) or with w <= 0 is dropped.  A signed-byte band enters as
+ *     0..255, like bilinear.
+ *  4. AVERAGE: accW += w, accR += d * w in scan order (fp64); accW < 0.00001
+ *     gives the window fill, else r = accR / accW.
+ *  5. MODE: taps of equal value form a class, a NaN tap that is not nodata a
+ *     class of its own; a class weighs the sum of its taps' w in scan order;
+ *     r is the value of the heaviest class, ties going to the class whose
+ *     first tap comes first.  No surviving tap gives the window fill.
+ *  6. Float32 results are cast, integer results go through floor(r + 0.5) and
+ *     saturate.
+ *  7. Rasters of the mask layer warp by nearest neighbour under both rules:
+ *     bit fields can be neither averaged nor voted.
+ * Differences from GDAL: the footprint is linearised from the pixel centre's
+ * neighbours (GDAL transforms the pixel's corners), weights are fractional
+ * coverages along each axis, and the taps are capped at 8 x 8 by striding.
+ * With hx = hy = 0.5 AVERAGE takes the bilinear rule's taps and weights; an
+ * aligned 2:1 footprint gives the 2 x 2 block mean.  Accepted wherever
+ * GSKYHIP_RESAMPLE_CUBIC is. */
+#define GSKYHIP_RESAMPLE_AVERAGE 3
+#define GSKYHIP_RESAMPLE_MODE 4
 
 /* Warp + merge + scale + palette for a batch of tiles, replacing per tile:
  * gRPC warp fan-out (tile_grpc.go:200-289 -> warp.go:82-382), RasterMerger
