@@ -686,14 +686,16 @@ def test_drill_deciles_parity(gpu, oracle, dcount, pc, clip):
 
 @pytest.mark.parametrize("side", [100, 150, 290])
 def test_drill_deciles_large_polygon(gpu, oracle, side):
-    """Long segments: 100 x 100 and 150 x 150 in-mask windows (~9.5k / ~21k
-    keys) take the wave-per-segment select, 290 x 290 (~80k keys, past its
-    2^16 limit) the 256-thread workgroup select streaming its values on every
-    pass; all equal to the oracle for every band, nodata values (-9999 at
-    1 %) skipped.  Bands 0/1/3 take
-    the bucket + counting-compare path (band 3: both signs, no shared key
-    bits); bands 2 and 4 (a handful of distinct values) overflow the 64-key
-    buckets and finish by radix selection."""
+    """Long segments: 100 x 100, 150 x 150 and 290 x 290 in-mask windows
+    (~9.5k / ~21k / ~80k keys), all past the 2048 keys a select workgroup
+    caches in LDS: decile_select_kernel, one 256-thread workgroup per
+    (polygon, band), streams the segment on every pass; all equal to the
+    oracle for every band, nodata values (-9999 at 1 %) skipped.  Bands 0/1/3
+    resolve their ranks in one pass: a 2048-bucket histogram of the key range,
+    then the 64-lane counting select of each rank's bucket (band 3: both signs,
+    no shared key bits); bands 2 and 4 (a handful of distinct values) overflow
+    the 64-key buckets and continue by range refinement on the bucket's key
+    range, down to a single key."""
     import torch
 
     from gsky_amd import drill
