@@ -22,8 +22,9 @@
 //     planner marked `inside` (RowRec.inside: every window pixel's source
 //     pixel lies in the band) takes the fast body: truncate, index, load, and
 //     a fold that is one compare + one select -- (v != nd) ? v : c, or in fill
-//     mode (c == nd) ? v : c, which is "v != nd && c == nd" without the
-//     second compare -- so no lane-mask logic lands on the scalar unit;
+//     mode (c == nd) ? v : c, which for integers is "v != nd && c == nd"
+//     without the second compare (float32 makes both: nn_fill_take()) -- so
+//     no lane-mask logic lands on the scalar unit;
 //   * everything else (window edges inside the block, POOL rows with their
 //     leaves, failed transforms) takes the general body with the per-pixel
 //     tests of the reference;
@@ -40,7 +41,9 @@
 //     255 and canvases never created are 0); 8 non-temporal 4-B stores per
 //     lane and row, each 256 contiguous bytes per wave.
 // Every body computes the reference's expressions, so all of them agree bit
-// for bit with oracle/ (tests/test_gpu_parity.py, tests/test_gpu_full.py).
+// for bit with oracle/ (tests/test_gpu_parity.py, tests/test_gpu_full.py) and
+// with the rule in numpy, each body at its own edges (tests/test_nn_rule.py,
+// tests/test_nn_edges.py).
 #pragma once
 #ifdef GSKYHIP_AB
 #include <cstdlib>
@@ -87,11 +90,23 @@ __device__ __forceinline__ uint32_t scale_int(const ScaleK &k, int32_t c) {
   return c == k.noData.i ? 0xFFu : b;
 }
 
+// Fill-mode take of the fast bodies (nn_fix_row, the fp64 fast body,
+// nn_partial_row).  Integer types: c == nd alone stands for the general
+// rule's "v != nd && c == nd", because v == nd == c leaves c's bits as they
+// are.  float32 tests v as well: -0.0 == 0.0 holds for the values and not
+// for the bits, so a -0.0 under a nodata of 0.0 would replace the canvas's
+// +0.0 (tests/test_nn_edges.py, A4).
+template <typename T>
+__device__ __forceinline__ bool nn_fill_take(typename VOf<T>::type c, typename VOf<T>::type v,
+                                             typename VOf<T>::type nd) {
+  if constexpr (std::is_same<T, float>::value) return (c == nd) & (v != nd);
+  else return c == nd;
+}
+
 // The fold of one `inside` LINEAR row whose window edge falls inside the
 // block: the fast body plus the window test (pixels outside the window read
-// nothing and fold nothing; fill mode takes v where c is nodata, which equals
-// the general rule's "v != nd && c == nd" because v == nd == c leaves c
-// unchanged).  Halves of 4 pixels keep the register peak of the fast body.
+// nothing and fold nothing; fill mode: nn_fill_take()).  Halves of 4 pixels
+// keep the register peak of the fast body.
 // The window is [wlo, whi) (wlo 0 and whi the window width, or a row's
 // in-band span).
 template <typename T, int NPX>
@@ -118,7 +133,7 @@ __device__ __forceinline__ void nn_partial_row(__amdgpu_buffer_rsrc_t rs, double
 #pragma unroll
     for (int q = 0; q < 4; q++) {
       const bool inw = (unsigned)(ic0 + 64 * (h + q) - wlo) < wn;
-      c[h + q] = (inw & (fill_mode ? (c[h + q] == nd) : (vv[q] != nd))) ? vv[q] : c[h + q];
+      c[h + q] = (inw & (fill_mode ? nn_fill_take<T>(c[h + q], vv[q], nd) : (vv[q] != nd))) ? vv[q] : c[h + q];
     }
   }
 }
@@ -175,7 +190,7 @@ __device__ __forceinline__ bool nn_fix_row(__amdgpu_buffer_rsrc_t rs, int64_t fx
   } else {
 #pragma unroll
     for (int q = 0; q < NPX; q++) {
-      bool take = c[q] == nd;
+      bool take = nn_fill_take<T>(c[q], vv[q], nd);
       if constexpr (PART) take = take & ((unsigned)(ic0 + 64 * q) < (unsigned)lim);
       c[q] = take ? vv[q] : c[q];
     }
@@ -374,15 +389,14 @@ __device__ __forceinline__ void nn_entry_core(const RenderArgs &a, const EntryD 
       for (int q = 0; q < NPX; q++) c[q] = (vv[q] != nd) ? vv[q] : c[q];
     } else {
 #pragma unroll
-      for (int q = 0; q < NPX; q++) c[q] = (c[q] == nd) ? vv[q] : c[q];
+      for (int q = 0; q < NPX; q++) c[q] = nn_fill_take<T>(c[q], vv[q], nd) ? vv[q] : c[q];
     }
     return;
   }
   if (kind == ROW_LINEAR && inside && !masked) {
     // window edge inside the block on an `inside` row: the fast body plus the
     // window test (pixels outside the window read nothing and fold nothing;
-    // fill mode takes v where c is nodata, which equals the general rule's
-    // "v != nd && c == nd" because v == nd == c leaves c unchanged)
+    // fill mode: nn_fill_take())
     nn_partial_row<T, NPX>(rs, ru.v(0), ru.v(1), ru.v(2), ru.v(3), ic0, 0, lim, bx, nd, fill_mode, c);
     return;
   }
