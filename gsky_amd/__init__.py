@@ -17,6 +17,8 @@ _LAZY = {
     "raster_merger_run": "raster", "scale": "raster", "scale_legacy": "raster",
     "GranuleSet": "tiles", "PipelinedBatch": "tiles", "RenderGraph": "tiles", "TileBatch": "tiles",
     "bbox_to_geot": "tiles", "WarpService": "service",
+    "FusionLayer": "fusion", "LayerCanvases": "fusion", "fuse": "fusion", "render_fused": "fusion",
+    "fuse_weighted": "fusion",
 }
 
 __version__ = "0.1.0"

@@ -92,6 +92,15 @@ class FlexRasterC(C.Structure):
                 ("polygon_hash", C.c_uint32), ("_pad", C.c_int32)]
 
 
+FUSE_MAX_LAYERS = 8
+
+
+class FuseLayer(C.Structure):
+    """gskyhip_fuse_layer: one input layer of gskyhip_fuse_layers / _render."""
+    _fields_ = [("canvases", C.c_void_p), ("dtype", C.c_int32), ("_pad", C.c_int32), ("nodata", C.c_double),
+                ("sp", ScaleParams), ("present", C.c_void_p)]
+
+
 # every symbol include/gskyhip.h declares (checked by tests/test_abi.py)
 EXPORTS = [
     "gskyhip_crs_from_srs", "gskyhip_crs_transform", "gskyhip_register_granule", "gskyhip_unregister_all", "warp_operation_fast",
@@ -114,6 +123,7 @@ EXPORTS = [
     "gskyhip_netcdf_info", "gskyhip_netcdf_srs", "gskyhip_netcdf_read_host", "gskyhip_netcdf_read", "gskyhip_register_netcdf",
     "gskyhip_overview_levels", "gskyhip_build_overviews", "gskyhip_register_geotiff_ovr", "gskyhip_register_netcdf_ovr",
     "gskyhip_service_register_granule_ovr",
+    "gskyhip_fuse_layers", "gskyhip_fuse_render",
 ]
 
 _lib = None
@@ -184,6 +194,11 @@ def lib() -> C.CDLL:
     L.gskyhip_gradient_palette.argtypes = [vp, ci, ci, vp]
     L.gskyhip_encode_rgba.argtypes = [C.POINTER(vp), ci, ci, ci, vp, vp, vp]
     L.gskyhip_compute_mask.argtypes = [vp, ci, i64, C.POINTER(Mask), vp, vp]
+    if hasattr(L, "gskyhip_fuse_layers"):   # absent from kept earlier builds (GSKYHIP_LIB=<name>)
+        L.gskyhip_fuse_layers.argtypes = [C.POINTER(FuseLayer), ci, ci, vp, ci, ci, ci, ci, vp, vp,
+                                          C.POINTER(i32), vp]
+        L.gskyhip_fuse_render.argtypes = [C.POINTER(FuseLayer), ci, ci, vp, ci, ci, ci, ci,
+                                          C.POINTER(ScaleParams), vp, vp, vp, vp, vp]
     L.gskyhip_drill_rows.argtypes = [ci, ci]
     L.gskyhip_drill.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, ci, C.c_float, C.c_float, C.c_float, ci, ci,
                                 vp, vp, vp]

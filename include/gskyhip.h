@@ -588,6 +588,90 @@ int gskyhip_encode_rgba(const uint8_t *const *bands, int nbands, int w, int h,
 int gskyhip_compute_mask(const void *data, int dtype, int64_t n, const gskyhip_mask *mask,
                          uint8_t *out, void *stream);
 
+/* ---- layer fusion (input_layers) ---------------------------------------- */
+/* TilePipeline.processDeps (processor/tile_pipeline.go:196-324): a layer with
+ * input_layers renders each dependent layer, scales it with that layer's own
+ * ScaleParams, names the results fuse<j> (getFlexRaster, 482-632: polygon
+ * "dummy_polygon", timestamps t, t-1 s, t-2 s, ... in layer order) and lets
+ * RasterMerger fold them: layer 0 wins, every later layer only fills what is
+ * still nodata.  Here the dependent layers are already rendered: layer l is
+ * the typed canvases of gskyhip_render_tiles' canvas_out layout -- tile t,
+ * namespace slot s at byte (t * n_ns + s) * max_w * max_h * 4, rows max_w
+ * elements apart -- with one value type T_l, one nodata n_l, its ScaleParams
+ * and an optional per-tile `present` flag (the reference's EmptyTile result
+ * and its effective-date `continue`, 216-240, 264-269).
+ *
+ * The rule, per tile, namespace slot and pixel.  T(x) is Go's conversion of
+ * the float64 x to the value type.
+ *   Per-layer stage.  A layer is scaled when fusion_unscale == 0 and its
+ *   (offset, scale, clip) are not all zero (251-253).
+ *     scaled: the pixel is utils.Scale of it (raster_scaler.go:30-332) with
+ *       colour_scale 0 -- the inner ScaleParams are built without it
+ *       (254-257) -- the type becomes Byte and the nodata 0xFF (272).  The
+ *       inner scale is never an auto-scale.
+ *     unscaled: the pixel keeps its type.  Where layer 0 is unscaled and
+ *       present on the tile it is the normalisation reference (283-286): if
+ *       T(n_0) != T(n_l), pixels equal to T(n_l) become T(n_0) and the
+ *       layer's nodata becomes n_0 (getFlexRaster's `normalise`).  With a NaN
+ *       nodata the comparisons fall out as in Go: always "different", never
+ *       "equal".
+ *     The input canvases are never written (the reference's in-place Byte
+ *     scale is not observable here).
+ *   Fold.  p0 is the first present layer.  The fused canvas has p0's
+ *     post-stage type, its nodata C is p0's post-stage nodata, and it starts
+ *     as T(C).  p0 writes where v != T(n'); every later present layer writes
+ *     where v != T(n') && canvas == T(n'), n' its OWN post-stage nodata
+ *     (MergeMaskedRaster, tile_merger.go:38-225, fill mode: the timestamps
+ *     decrease strictly).
+ *   Type check.  Every layer's post-stage type must be the same, else
+ *     GSKYHIP_E_TYPE (the reference would reinterpret the canvas bytes and
+ *     panic).
+ * Deviations from the reference:
+ *   - its allFilled early stop (252, 300-305) is dead code: allFilled starts
+ *     false and is only ever assigned false.  The kernels skip a layer's reads
+ *     for a wave whose pixels that layer cannot fill, which changes no value;
+ *   - a tile with no present layer gets a canvas of layer 0's post-stage
+ *     nodata (C = n_0 for an unscaled layer 0) and transparent RGBA; the
+ *     reference pushes a zero Byte "EmptyTile_dummy" raster (314-320): the
+ *     same RGBA, another canvas;
+ *   - where layer 0 is absent nothing is normalised; the reference can still
+ *     normalise Byte layers against the EmptyTile raster. */
+#define GSKYHIP_FUSE_MAX_LAYERS 8
+typedef struct {
+    const void *canvases;        /* dev: n_tiles x n_ns slots, see above         */
+    int32_t dtype;               /* Byte, SignedByte, Int16, UInt16 or Float32   */
+    int32_t _pad;
+    double nodata;
+    gskyhip_scale_params sp;     /* the layer's own ScaleParams                   */
+    const uint8_t *present;      /* dev uint8[n_tiles], or NULL: all present      */
+} gskyhip_fuse_layer;
+
+/* The fused typed canvases.  layers: HOST array in input_layers order, 1 ..
+ * GSKYHIP_FUSE_MAX_LAYERS; n_ns: 1 or 3; tiles: dev (width, height used);
+ * canvas_out: dev, the layout of the inputs (pixels outside a tile's width x
+ * height are left alone); nodata_out: dev double per tile, C; dtype_out: HOST,
+ * the fused type.  One kernel on `stream`: no allocation, no copy, no
+ * synchronisation, so the call can be captured in a graph.  Every argument
+ * error (GSKYHIP_E_ARG: NULL pointer, n_layers, n_ns, sizes; GSKYHIP_E_TYPE:
+ * a layer's value type, mixed post-stage types) returns before any HIP call. */
+int gskyhip_fuse_layers(const gskyhip_fuse_layer *layers, int n_layers, int n_ns,
+                        const gskyhip_tile *tiles, int n_tiles, int max_w, int max_h,
+                        int fusion_unscale, void *canvas_out, double *nodata_out,
+                        int32_t *dtype_out, void *stream);
+
+/* The same, then the OUTER utils.Scale (outer_sp, colour_scale honoured,
+ * nodata C) and the EncodePNG pixel rule (ogc_encoders.go:86-133; ramp: dev
+ * 256 x RGBA or NULL for grey, ignored for n_ns = 3) in the same pass:
+ * rgba_out dev n_tiles x max_h x max_w x 4.  canvas_out and nodata_out may be
+ * NULL.  An outer auto-scale (offset = scale = clip = 0) needs a reduction
+ * over the fused canvas and returns GSKYHIP_E_ARG: call gskyhip_fuse_layers,
+ * then gskyhip_scale. */
+int gskyhip_fuse_render(const gskyhip_fuse_layer *layers, int n_layers, int n_ns,
+                        const gskyhip_tile *tiles, int n_tiles, int max_w, int max_h,
+                        int fusion_unscale, const gskyhip_scale_params *outer_sp,
+                        const uint8_t *ramp, uint8_t *rgba_out, void *canvas_out,
+                        double *nodata_out, void *stream);
+
 /* ---- output codecs ------------------------------------------------------ */
 /* png.Encode of EncodePNG (utils/ogc_encoders.go:139; Go 1.12 image/png) for
  * a batch of RGBA tiles in HBM, e.g. the rgba_out of gskyhip_render_tiles:
