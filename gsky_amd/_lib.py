@@ -124,7 +124,19 @@ EXPORTS = [
     "gskyhip_overview_levels", "gskyhip_build_overviews", "gskyhip_register_geotiff_ovr", "gskyhip_register_netcdf_ovr",
     "gskyhip_service_register_granule_ovr",
     "gskyhip_fuse_layers", "gskyhip_fuse_render",
+    "gskyhip_inflate_blocks", "gskyhip_inflate_blocks_host", "gskyhip_geotiff_read_decode",
+    "gskyhip_netcdf_read_decode", "gskyhip_register_geotiff_decode", "gskyhip_register_netcdf_decode",
 ]
+
+DECODE_HOST, DECODE_DEVICE = 0, 1
+
+
+def decode_mode(name) -> int:
+    """"host" / "device" -> GSKYHIP_DECODE_*."""
+    try:
+        return {"host": DECODE_HOST, "device": DECODE_DEVICE}[name]
+    except (KeyError, TypeError):
+        raise ValueError('decode must be "host" or "device", not %r' % (name,))
 
 _lib = None
 
@@ -160,6 +172,13 @@ def lib() -> C.CDLL:
         L.gskyhip_register_netcdf_ovr.argtypes = [C.c_char_p, ci, ci, ci]
         L.gskyhip_service_register_granule_ovr.argtypes = [C.c_char_p, C.c_char_p, ci, C.POINTER(Granule), vp,
                                                            C.c_char_p, ci, ci]
+    if hasattr(L, "gskyhip_inflate_blocks"):   # absent from kept earlier builds (GSKYHIP_LIB=<name>)
+        L.gskyhip_inflate_blocks.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp, vp]
+        L.gskyhip_inflate_blocks_host.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, ci, vp, vp]
+        L.gskyhip_geotiff_read_decode.argtypes = [C.c_char_p, ci, ci, vp, i64, ci, vp, vp]
+        L.gskyhip_netcdf_read_decode.argtypes = [C.c_char_p, ci, vp, i64, ci, vp, vp]
+        L.gskyhip_register_geotiff_decode.argtypes = [C.c_char_p, ci, ci, ci, ci]
+        L.gskyhip_register_netcdf_decode.argtypes = [C.c_char_p, ci, ci, ci, ci]
     L.warp_operation_fast.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(d), vp, C.c_char_p, C.POINTER(d),
                                       ci, ci, ci, ci, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci),
                                       C.POINTER(d), C.POINTER(ci), C.POINTER(ci)]

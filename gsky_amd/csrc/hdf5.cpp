@@ -750,6 +750,74 @@ bool unfilter(const Var &v, const std::vector<uint8_t> &in, uint32_t mask, uint6
   return true;
 }
 
+// The chunk index of a chunked variable, for every index type open() parses:
+// a chunk by its element offset, or nullptr when it was never written.
+struct ChunkIndex {
+  std::map<std::vector<uint64_t>, ChunkRef> idx;   // v1 B-tree / single chunk: by offset
+  std::vector<ChunkRef> by_linear;                 // implicit / fixed array: by linear chunk index
+  std::vector<uint64_t> nchunks;
+  uint64_t cbytes = 0;
+  ChunkRef tmp;
+
+  bool build(Rd &r, const File &f, const Var &v) {
+    const int rank = (int)v.shape.size();
+    cbytes = (uint64_t)v.esize;
+    for (uint64_t c : v.chunk) cbytes *= c;
+    nchunks.assign(rank, 0);
+    uint64_t total_chunks = 1;
+    for (int k = 0; k < rank; k++) {
+      if (v.chunk[k] == 0) return false;
+      nchunks[k] = (v.shape[k] + v.chunk[k] - 1) / v.chunk[k];
+      total_chunks *= nchunks[k];
+      if (total_chunks > ((uint64_t)1 << 32)) return false;   // a corrupt shape / chunk size
+    }
+    if (v.index_type == 0) {
+      uint64_t visited = 0;
+      if (v.addr != kUndef && !chunk_index_v1(r, v.addr, rank, idx, 0, visited)) return false;
+    } else if (v.index_type == 1) {
+      if (v.addr != kUndef) {
+        ChunkRef c{v.addr, v.single_size ? v.single_size : cbytes, v.single_mask};
+        idx[std::vector<uint64_t>(rank, 0)] = c;
+      }
+    } else if (v.index_type == 2) {
+      for (uint64_t i = 0; i < total_chunks; i++) by_linear.push_back({v.addr + i * cbytes, cbytes, 0});
+    } else if (v.index_type == 3) {   // fixed array header "FAHD" -> data block "FADB" (unpaged)
+      if (!r.sig(v.addr, "FAHD")) return false;
+      const int client = (int)r.u(v.addr + 5, 1), esz = (int)r.u(v.addr + 6, 1), bits = (int)r.u(v.addr + 7, 1);
+      const uint64_t nent = r.len(v.addr + 8);
+      const uint64_t db = r.addr(v.addr + 8 + f.len_size);
+      if (nent > ((uint64_t)1 << bits) || !r.sig(db, "FADB")) return false;   // paged data blocks: not covered
+      const uint64_t e0 = db + 6 + f.off_size;
+      for (uint64_t i = 0; i < nent; i++) {
+        const uint64_t e = e0 + i * esz;
+        ChunkRef c{r.addr(e), cbytes, 0};
+        if (client == 1) {
+          const int csz = esz - f.off_size - 4;
+          c.size = r.u(e + f.off_size, csz);
+          c.mask = (uint32_t)r.u(e + f.off_size + csz, 4);
+        }
+        by_linear.push_back(c);
+      }
+    } else {
+      return false;
+    }
+    return r.ok;
+  }
+
+  const ChunkRef *find(const Var &v, const std::vector<uint64_t> &off) {
+    const ChunkRef *c = nullptr;
+    if (!by_linear.empty()) {
+      uint64_t li = 0;
+      for (size_t k = 0; k < off.size(); k++) li = li * nchunks[k] + off[k] / v.chunk[k];
+      if (li < by_linear.size()) { tmp = by_linear[li]; c = &tmp; }
+    } else {
+      auto it = idx.find(off);
+      if (it != idx.end()) c = &it->second;
+    }
+    return (c && c->addr != kUndef) ? c : nullptr;
+  }
+};
+
 // Fill bytes of one element, file order: the dataset's fill-value message
 // (what HDF5 returns for storage never written, and what netCDF-C reads back),
 // else the _FillValue attribute, else netCDF-C's NC_FILL_* default of the
@@ -894,55 +962,9 @@ bool read(const File &f, const Var &v, uint64_t start, uint64_t count, uint8_t *
   if (start % trail || count % trail) return false;
   lo[0] = start / trail;
   hi[0] = (start + count) / trail;
-  // chunk index
-  std::map<std::vector<uint64_t>, ChunkRef> idx;
-  uint64_t cbytes = es;
-  for (uint64_t c : v.chunk) cbytes *= c;
-  std::vector<uint64_t> nchunks(rank);
-  uint64_t total_chunks = 1;
-  for (int k = 0; k < rank; k++) {
-    if (v.chunk[k] == 0) return false;
-    nchunks[k] = (v.shape[k] + v.chunk[k] - 1) / v.chunk[k];
-    total_chunks *= nchunks[k];
-    if (total_chunks > ((uint64_t)1 << 32)) return false;   // a corrupt shape / chunk size
-  }
-  auto linear_chunk = [&](const std::vector<uint64_t> &off) {
-    uint64_t li = 0;
-    for (int k = 0; k < rank; k++) li = li * nchunks[k] + off[k] / v.chunk[k];
-    return li;
-  };
-  std::vector<ChunkRef> by_linear;   // implicit / fixed array: by linear chunk index
-  if (v.index_type == 0) {
-    uint64_t visited = 0;
-    if (v.addr != kUndef && !chunk_index_v1(r, v.addr, rank, idx, 0, visited)) return false;
-  } else if (v.index_type == 1) {
-    if (v.addr != kUndef) {
-      ChunkRef c{v.addr, v.single_size ? v.single_size : cbytes, v.single_mask};
-      idx[std::vector<uint64_t>(rank, 0)] = c;
-    }
-  } else if (v.index_type == 2) {
-    for (uint64_t i = 0; i < total_chunks; i++) by_linear.push_back({v.addr + i * cbytes, cbytes, 0});
-  } else if (v.index_type == 3) {   // fixed array header "FAHD" -> data block "FADB" (unpaged)
-    if (!r.sig(v.addr, "FAHD")) return false;
-    const int client = (int)r.u(v.addr + 5, 1), esz = (int)r.u(v.addr + 6, 1), bits = (int)r.u(v.addr + 7, 1);
-    const uint64_t nent = r.len(v.addr + 8);
-    const uint64_t db = r.addr(v.addr + 8 + f.len_size);
-    if (nent > ((uint64_t)1 << bits) || !r.sig(db, "FADB")) return false;   // paged data blocks: not covered
-    const uint64_t e0 = db + 6 + f.off_size;
-    for (uint64_t i = 0; i < nent; i++) {
-      const uint64_t e = e0 + i * esz;
-      ChunkRef c{r.addr(e), cbytes, 0};
-      if (client == 1) {
-        const int csz = esz - f.off_size - 4;
-        c.size = r.u(e + f.off_size, csz);
-        c.mask = (uint32_t)r.u(e + f.off_size + csz, 4);
-      }
-      by_linear.push_back(c);
-    }
-  } else {
-    return false;
-  }
-  if (!r.ok) return false;
+  ChunkIndex ci;
+  if (!ci.build(r, f, v)) return false;
+  const uint64_t cbytes = ci.cbytes;
   const std::vector<uint8_t> fb = fill_bytes(v);
   // every chunk meeting the box
   std::vector<uint64_t> c0(rank), c1(rank), cc(rank);
@@ -957,16 +979,8 @@ bool read(const File &f, const Var &v, uint64_t start, uint64_t count, uint8_t *
   for (;;) {
     std::vector<uint64_t> off(rank);
     for (int k = 0; k < rank; k++) off[k] = cc[k] * v.chunk[k];
-    const ChunkRef *c = nullptr;
-    ChunkRef tmp;
-    if (!by_linear.empty()) {
-      const uint64_t li = linear_chunk(off);
-      if (li < by_linear.size()) { tmp = by_linear[li]; c = &tmp; }
-    } else {
-      auto it = idx.find(off);
-      if (it != idx.end()) c = &it->second;
-    }
-    bool have = c && c->addr != kUndef;
+    const ChunkRef *c = ci.find(v, off);
+    bool have = c != nullptr;
     if (have) {
       if (!r.has(c->addr, c->size)) return false;
       raw.assign(f.buf.begin() + c->addr, f.buf.begin() + (c->addr + c->size));
@@ -1001,6 +1015,51 @@ bool read(const File &f, const Var &v, uint64_t start, uint64_t count, uint8_t *
       }
       if (k < 0) break;
     }
+    int k = rank - 1;
+    for (; k >= 0; k--) {
+      if (++cc[k] < c1[k]) break;
+      cc[k] = c0[k];
+    }
+    if (k < 0) break;
+  }
+  return true;
+}
+
+std::vector<uint8_t> fill_value(const Var &v) { return fill_bytes(v); }
+
+bool chunks(const File &f, const Var &v, uint64_t start, uint64_t count, std::vector<ChunkInfo> &out) {
+  out.clear();
+  Rd r{f};
+  const int rank = (int)v.shape.size();
+  uint64_t total = 1;
+  for (uint64_t d : v.shape) total *= d;
+  if (v.layout != 2 || rank == 0 || v.esize == 0 || count == 0 || start > total || count > total - start) return false;
+  uint64_t trail = 1;
+  for (int k = 1; k < rank; k++) trail *= v.shape[k];
+  if (trail == 0 || start % trail || count % trail) return false;
+  std::vector<uint64_t> lo(rank, 0), hi(v.shape);
+  lo[0] = start / trail;
+  hi[0] = (start + count) / trail;
+  ChunkIndex ci;
+  if (!ci.build(r, f, v)) return false;
+  std::vector<uint64_t> c0(rank), c1(rank), cc(rank);
+  for (int k = 0; k < rank; k++) {
+    c0[k] = lo[k] / v.chunk[k];
+    c1[k] = (hi[k] + v.chunk[k] - 1) / v.chunk[k];
+    cc[k] = c0[k];
+  }
+  for (;;) {
+    ChunkInfo info;
+    info.offset.resize(rank);
+    for (int k = 0; k < rank; k++) info.offset[k] = cc[k] * v.chunk[k];
+    if (const ChunkRef *c = ci.find(v, info.offset)) {
+      if (!r.has(c->addr, c->size)) return false;
+      info.present = true;
+      info.addr = c->addr;
+      info.size = c->size;
+      info.mask = c->mask;
+    }
+    out.push_back(std::move(info));
     int k = rank - 1;
     for (; k >= 0; k--) {
       if (++cc[k] < c1[k]) break;

@@ -86,5 +86,22 @@ bool is_hdf5(const std::vector<uint8_t> &buf);
 // (count * v.esize bytes, the file's byte order); false on a read error.
 bool read(const File &f, const Var &v, uint64_t start, uint64_t count, uint8_t *out);
 
+// One chunk of a chunked variable as its index records it (nothing is read).
+struct ChunkInfo {
+  bool present = false;           // false: never written (reads as the fill value)
+  uint64_t addr = 0, size = 0;    // file address and stored (filtered) bytes, inside the file
+  uint32_t mask = 0;              // filter mask: bit i set -- filter i of the pipeline was skipped
+  std::vector<uint64_t> offset;   // element offset of the chunk in the variable, per dimension
+};
+
+// The chunks that elements [start, start + count) of a chunked variable touch
+// (whole trailing dimensions, as read() takes them), in row-major chunk
+// order, for every chunk index type open() parses.  False: not chunked, a
+// range read() refuses, or a broken index.
+bool chunks(const File &f, const Var &v, uint64_t start, uint64_t count, std::vector<ChunkInfo> &out);
+
+// One element of the value read() gives storage never written, file order.
+std::vector<uint8_t> fill_value(const Var &v);
+
 }  // namespace h5
 }  // namespace gsky

@@ -846,6 +846,9 @@ struct DropIn {
   // (path, band) ingested by the _ovr calls -> (method, min_size): a re-read of the
   // file (changed on disk, or evicted and requested again) builds the same pyramid
   std::map<std::pair<std::string, int>, std::pair<int, int>> ovr_asked;
+  // where a registered file's blocks are decoded when it is read again
+  // (gskyhip_register_*_decode; absent: the host)
+  std::map<std::pair<std::string, int>, int> decode_asked;
   std::map<std::string, std::shared_ptr<struct GeoLocEntry>> geolocs;   // by GeoLocOpts (geoloc_entry)
 };
 DropIn &dropin() {
@@ -917,6 +920,7 @@ bool have_gpu() {
 struct OvrBuild {
   int method = -1, min_size = 0;
   bool strict = false;
+  int decode = GSKYHIP_DECODE_HOST;   // where the file's blocks are decoded (gskyhip_register_*_decode)
 };
 
 bool ovr_type_ok(int dtype) {
@@ -986,7 +990,10 @@ int ingest_geotiff_locked(DropIn &d, const std::string &path, int band, const Ov
     void *p = nullptr;
     if (hipMalloc(&p, (size_t)(xs * ys * ts)) != hipSuccess) return GSKYHIP_E_HIP;
     r.owned.push_back(p);
-    if ((rc = gskyhip_geotiff_read(path.c_str(), band, lv, p, xs * ys * ts, nullptr))) return rc;
+    rc = ob.decode == GSKYHIP_DECODE_HOST
+             ? gskyhip_geotiff_read(path.c_str(), band, lv, p, xs * ys * ts, nullptr)
+             : gskyhip_geotiff_read_decode(path.c_str(), band, lv, p, xs * ys * ts, ob.decode, nullptr, nullptr);
+    if (rc) return rc;
     if (build) break;   // the planned levels are built, not read
   }
   if (build && (rc = ovr_build(info, ob.method, r))) return rc;
@@ -1034,7 +1041,10 @@ int ingest_netcdf_locked(DropIn &d, const std::string &path, int band, const Ovr
   if (!r.stamped) r.fsize = 0;
   if (hipMalloc(&p, (size_t)bytes0) != hipSuccess) return GSKYHIP_E_HIP;
   r.owned.push_back(p);
-  if ((rc = gskyhip_netcdf_read(path.c_str(), band, p, bytes0, nullptr))) return rc;
+  rc = ob.decode == GSKYHIP_DECODE_HOST
+           ? gskyhip_netcdf_read(path.c_str(), band, p, bytes0, nullptr)
+           : gskyhip_netcdf_read_decode(path.c_str(), band, p, bytes0, ob.decode, nullptr, nullptr);
+  if (rc) return rc;
   if ((rc = ovr_build(info, ob.method, r))) return rc;
   gskyhip_granule &g = r.g;
   g.data = p;
@@ -1130,6 +1140,8 @@ RegPtr lookup_dataset(DropIn &d, const std::string &path, int band, int *irc) {
       ob.method = asked->second.first;
       ob.min_size = asked->second.second;
     }
+    const auto how = d.decode_asked.find({path, band});
+    if (how != d.decode_asked.end()) ob.decode = how->second;
     *irc = nc ? ingest_netcdf_locked(d, path, band, ob) : ingest_geotiff_locked(d, path, band, ob);
     if (*irc == 0) it = d.reg.find({path, band});
   }
@@ -1389,6 +1401,7 @@ int gskyhip_unregister_all(void) {
   std::lock_guard<std::mutex> lk(d.mu);
   d.reg.clear();       // HBM of ingested granules is freed once no batch in flight holds it
   d.ovr_asked.clear();
+  d.decode_asked.clear();
   d.geolocs.clear();
   return 0;
 }
@@ -1398,6 +1411,7 @@ int gskyhip_register_geotiff(const char *path, int band) {
   DropIn &d = dropin();
   std::lock_guard<std::mutex> lk(d.mu);
   d.ovr_asked.erase({path, band});
+  d.decode_asked.erase({path, band});
   return ingest_geotiff_locked(d, path, band, OvrBuild());
 }
 
@@ -1406,6 +1420,7 @@ int gskyhip_register_netcdf(const char *path, int band) {
   DropIn &d = dropin();
   std::lock_guard<std::mutex> lk(d.mu);
   d.ovr_asked.erase({path, band});
+  d.decode_asked.erase({path, band});
   return ingest_netcdf_locked(d, path, band, OvrBuild());
 }
 
@@ -1413,6 +1428,7 @@ int gskyhip_register_geotiff_ovr(const char *path, int band, int method, int min
   if (!path || (method != GSKYHIP_OVR_NEAREST && method != GSKYHIP_OVR_AVERAGE)) return GSKYHIP_E_ARG;
   DropIn &d = dropin();
   std::lock_guard<std::mutex> lk(d.mu);
+  d.decode_asked.erase({path, band});
   OvrBuild ob;
   ob.method = method; ob.min_size = min_size; ob.strict = true;
   const int rc = ingest_geotiff_locked(d, path, band, ob);
@@ -1424,11 +1440,40 @@ int gskyhip_register_netcdf_ovr(const char *path, int band, int method, int min_
   if (!path || (method != GSKYHIP_OVR_NEAREST && method != GSKYHIP_OVR_AVERAGE)) return GSKYHIP_E_ARG;
   DropIn &d = dropin();
   std::lock_guard<std::mutex> lk(d.mu);
+  d.decode_asked.erase({path, band});
   OvrBuild ob;
   ob.method = method; ob.min_size = min_size; ob.strict = true;
   const int rc = ingest_netcdf_locked(d, path, band, ob);
   if (rc == 0) d.ovr_asked[{path, band}] = {method, min_size};
   return rc;
+}
+
+static int register_decode(const char *path, int band, int method, int min_size, int decode, bool nc) {
+  if (!path || (method != -1 && method != GSKYHIP_OVR_NEAREST && method != GSKYHIP_OVR_AVERAGE) ||
+      (decode != GSKYHIP_DECODE_HOST && decode != GSKYHIP_DECODE_DEVICE))
+    return GSKYHIP_E_ARG;
+  DropIn &d = dropin();
+  std::lock_guard<std::mutex> lk(d.mu);
+  OvrBuild ob;
+  ob.decode = decode;
+  if (method < 0) {
+    d.ovr_asked.erase({path, band});
+  } else {
+    ob.method = method; ob.min_size = min_size; ob.strict = true;
+  }
+  const int rc = nc ? ingest_netcdf_locked(d, path, band, ob) : ingest_geotiff_locked(d, path, band, ob);
+  if (rc == 0 && method >= 0) d.ovr_asked[{path, band}] = {method, min_size};
+  if (rc == 0 && decode != GSKYHIP_DECODE_HOST) d.decode_asked[{path, band}] = decode;
+  else d.decode_asked.erase({path, band});
+  return rc;
+}
+
+int gskyhip_register_geotiff_decode(const char *path, int band, int ovr_method, int min_size, int decode) {
+  return register_decode(path, band, ovr_method, min_size, decode, false);
+}
+
+int gskyhip_register_netcdf_decode(const char *path, int band, int ovr_method, int min_size, int decode) {
+  return register_decode(path, band, ovr_method, min_size, decode, true);
 }
 
 }  // extern "C"

@@ -32,6 +32,23 @@
 // threads (zlib / LZW / PackBits are byte-serial), staged block-major in
 // pinned memory, copied to HBM in one transfer and placed row-major by
 // assemble_kernel (a thread per output element; edge blocks clipped).
+//
+// Device decode (gskyhip_geotiff_read_decode / gskyhip_netcdf_read_decode with
+// GSKYHIP_DECODE_DEVICE, opt-in): the band's *compressed* blocks are gathered
+// into pinned memory and copied to HBM in one transfer; Deflate blocks are
+// inflated there by inflate.hip (a wave per block), uncompressed ones are used
+// where they landed; unpredict_kernel undoes byte order and the TIFF
+// predictors in place (a wave per block row: prefix sums by wave scan with a
+// carry between 64-element pieces -- wrap-around addition is associative, so
+// the sums equal the serial loop's); place_tiff_kernel / place_nc_kernel pick
+// the band's sample, gather predictor 3's byte planes, undo the HDF5 shuffle,
+// clip edge blocks, flip south-up rows, write the fill value for chunks never
+// written and store rows into the band.  LZW, PackBits, fletcher32,
+// contiguous / compact and netCDF classic data take the host path inside the
+// same call.  One difference from the host path: a Deflate block may not
+// inflate to more than one full block (the host path tolerates up to one
+// further block of surplus, which no writer produces); the device path then
+// reports "capacity exceeded" and the call fails as for an undecodable file.
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 
@@ -563,12 +580,9 @@ extern "C" int gskyhip_geotiff_read_host(const char *path, int band, int level, 
   }
 }
 
-static int geotiff_read_impl(const char *path, int band, int level, void *dev_out, int64_t out_bytes,
-                                    void *stream) {
-  Tiff t;
-  const Ifd *d = nullptr;
-  int rc = open_level(path, band, level, t, d);
-  if (rc) return rc;
+// The host-decode device read of an opened level (gskyhip_geotiff_read).
+static int geotiff_read_opened(const Tiff &t, const Ifd *d, int band, void *dev_out, int64_t out_bytes, void *stream) {
+  int rc = 0;
   const int bytes = d->bits / 8;
   const int64_t n = d->width * d->height;
   if (!dev_out || out_bytes < n * bytes) return GSKYHIP_E_ARG;
@@ -598,10 +612,288 @@ static int geotiff_read_impl(const char *path, int band, int level, void *dev_ou
   return rc;
 }
 
+static int geotiff_read_impl(const char *path, int band, int level, void *dev_out, int64_t out_bytes,
+                                    void *stream) {
+  Tiff t;
+  const Ifd *d = nullptr;
+  int rc = open_level(path, band, level, t, d);
+  if (rc) return rc;
+  return geotiff_read_opened(t, d, band, dev_out, out_bytes, stream);
+}
+
 extern "C" int gskyhip_geotiff_read(const char *path, int band, int level, void *dev_out, int64_t out_bytes,
                                     void *stream) {
   try {
     return geotiff_read_impl(path, band, level, dev_out, out_bytes, stream);
+  } catch (...) {   // a malformed file (bad_alloc of a size it declares): never through the C ABI
+    return GSKYHIP_E_TYPE;
+  }
+}
+
+// ======================================================================== device decode
+namespace gsky {
+namespace {
+
+template <typename W>
+__device__ inline W bswap_w(W x) {
+  W y = 0;
+#pragma unroll
+  for (int k = 0; k < (int)sizeof(W); k++) y = (W)((y << 8) | ((x >> (8 * k)) & 0xFF));
+  return y;
+}
+
+template <typename W>
+__device__ inline W shfl_up_w(W v, int off) {
+  if constexpr (sizeof(W) == 8) {
+    const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, (unsigned)off);
+    const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), (unsigned)off);
+    return ((W)hi << 32) | lo;
+  } else {
+    return (W)__shfl_up((int)v, (unsigned)off);
+  }
+}
+
+template <typename W>
+__device__ inline W shfl_w(W v, int lane) {
+  if constexpr (sizeof(W) == 8) {
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, lane);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), lane);
+    return ((W)hi << 32) | lo;
+  } else {
+    return (W)__shfl((int)v, lane);
+  }
+}
+
+// One wave per (block, row), in place over the row's n elements of type W:
+// byte order (swap), then with scan the running sums v[i] += v[i - samples]
+// (TIFF predictor 2 over samples; predictor 3's first step over bytes).  The
+// row is taken in pieces of P = 64 - 64 % samples lanes, so that a lane keeps
+// its sample; within a piece a scan over lanes `samples` apart, between pieces
+// the last sum of each sample as the carry.  Rows past a short last strip are
+// not touched.
+template <typename W>
+__global__ __launch_bounds__(64) void unpredict_kernel(uint8_t *__restrict__ buf, const int64_t *__restrict__ blk_off,
+                                                       int64_t n_blocks, int64_t bh, int64_t across, int64_t height,
+                                                       int tiled, int64_t row_bytes, int64_t n, int samples, int swap,
+                                                       int scan) {
+  const int64_t job = blockIdx.x;
+  const int64_t blk = job / bh, r = job - blk * bh;
+  if (blk >= n_blocks) return;
+  const int64_t left = height - (blk / across) * bh;   // strips: the last one may be short
+  const int64_t rows = (tiled || left > bh) ? bh : left;
+  if (r >= rows) return;
+  W *row = (W *)(buf + blk_off[blk] + r * row_bytes);
+  const int lane = threadIdx.x;
+  const int P = 64 - 64 % samples;
+  const int carry_from = P - samples + lane % samples;
+  W carry = 0;
+  for (int64_t base = 0; base < n; base += P) {
+    const int64_t i = base + lane;
+    const bool active = lane < P && i < n;
+    W v = active ? row[i] : (W)0;
+    if (swap) v = bswap_w(v);
+    if (scan) {
+      for (int off = samples; off < P; off <<= 1) {
+        const W t = shfl_up_w(v, off);
+        if (lane >= off) v = (W)(v + t);
+      }
+      v = (W)(v + carry);
+      carry = shfl_w(v, carry_from);
+    }
+    if (active) row[i] = v;
+  }
+}
+
+// Output element (x, y) <- sample `band` of pixel (x % bw, y % bh) of its
+// block; planes: predictor 3's byte planes (most significant first) gathered.
+template <typename W>
+__global__ __launch_bounds__(256) void place_tiff_kernel(const uint8_t *__restrict__ buf,
+                                                         const int64_t *__restrict__ blk_off, W *__restrict__ out,
+                                                         int64_t width, int64_t height, int64_t bw, int64_t bh,
+                                                         int64_t across, int samples, int band, int planes) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= width * height) return;
+  const int64_t y = i / width, x = i - y * width;
+  const int64_t by = y / bh, bx = x / bw;
+  const int64_t n = bw * samples;   // elements of a block row
+  const uint8_t *row = buf + blk_off[by * across + bx] + (y - by * bh) * n * (int64_t)sizeof(W);
+  const int64_t e = (x - bx * bw) * samples + band;
+  if (!planes) {
+    out[i] = ((const W *)row)[e];
+  } else {
+    W v = 0;
+#pragma unroll
+    for (int k = 0; k < (int)sizeof(W); k++) v = (W)(v | ((W)row[(int64_t)((int)sizeof(W) - 1 - k) * n + e] << (8 * k)));
+    out[i] = v;
+  }
+}
+
+// Output element (x, y) of a netCDF-4 band <- its chunk: rows south-up when
+// bottom_up, the HDF5 shuffle undone (byte b of element e at b * ne + e), the
+// fill value for a chunk never written (offset < 0), file byte order -> host.
+template <typename W>
+__global__ __launch_bounds__(256) void place_nc_kernel(const uint8_t *__restrict__ buf,
+                                                       const int64_t *__restrict__ chunk_off,
+                                                       const uint8_t *__restrict__ chunk_shuffled, W *__restrict__ out,
+                                                       int64_t nx, int64_t ny, int64_t cy, int64_t cx, int64_t ncx,
+                                                       int64_t lead, int64_t ne, int bottom_up, int swap, W fill) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nx * ny) return;
+  const int64_t y = i / nx, x = i - y * nx;
+  const int64_t yy = bottom_up ? ny - 1 - y : y;
+  const int64_t ky = yy / cy, kx = x / cx;
+  const int64_t k = ky * ncx + kx;
+  const int64_t e = (lead * cy + (yy - ky * cy)) * cx + (x - kx * cx);
+  const int64_t off = chunk_off[k];
+  W v = fill;
+  if (off >= 0) {
+    if (chunk_shuffled[k]) {
+      v = 0;
+#pragma unroll
+      for (int b = 0; b < (int)sizeof(W); b++) v = (W)(v | ((W)buf[off + (int64_t)b * ne + e] << (8 * b)));
+    } else {
+      v = ((const W *)(buf + off))[e];
+    }
+  }
+  if (swap) v = bswap_w(v);
+  out[i] = v;
+}
+
+inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+
+// Pinned staging + one device buffer for a device decode, freed on return.
+struct DecodeBuffers {
+  uint8_t *pinned = nullptr, *dev = nullptr;
+  ~DecodeBuffers() {
+    if (dev) (void)hipFree(dev);
+    if (pinned) (void)hipHostFree(pinned);
+  }
+};
+
+// An opened GeoTIFF level with the block decode on the device (compression
+// 1, 8, 32946).  stats as gskyhip_geotiff_read_decode documents them.
+int geotiff_read_device(const Tiff &t, const Ifd &d, int band, void *dev_out, int64_t out_bytes, int64_t *stats,
+                        void *stream) {
+  const int bytes = d.bits / 8;
+  const int64_t npix = d.width * d.height;
+  if (!dev_out || out_bytes < npix * bytes) return GSKYHIP_E_ARG;
+  const Layout L = layout_of(d);
+  const int64_t nblk = L.across * L.down;
+  const int64_t plane0 = d.planar == 2 ? (int64_t)(band - 1) * nblk : 0;
+  if ((int64_t)d.offsets.size() < plane0 + nblk || nblk > (1 << 30)) return GSKYHIP_E_TYPE;
+  const bool deflate = d.compression != 1;
+  const int64_t row_bytes = L.bw * L.samples * bytes, full = row_bytes * L.bh;
+  // the unified device buffer: [compressed blocks | per-block offsets | decoded blocks]
+  std::vector<int64_t> in_off(nblk), in_len(nblk), out_off(nblk), out_cap(nblk), out_need(nblk), blk_off(nblk);
+  int64_t at = 0, moved = 0;
+  for (int64_t i = 0; i < nblk; i++) {
+    const uint64_t off = d.offsets[plane0 + i], cnt = d.counts[plane0 + i];
+    if (off > t.buf.size() || cnt > t.buf.size() - off) return GSKYHIP_E_TYPE;
+    // strips: the last one holds only the image's remaining rows
+    const int64_t rows = d.tiled ? L.bh : std::min<int64_t>(L.bh, d.height - (i / L.across) * L.bh);
+    out_need[i] = row_bytes * rows;
+    out_cap[i] = full;
+    if (!deflate && (int64_t)cnt < out_need[i]) return GSKYHIP_E_TYPE;
+    if (deflate && cnt > 0xFFFFFFFFull) return GSKYHIP_E_TYPE;
+    in_off[i] = at;
+    in_len[i] = deflate ? (int64_t)cnt : out_need[i];
+    at = align16(at + in_len[i]);
+    moved += in_len[i];
+  }
+  const int64_t comp_bytes = std::max<int64_t>(at, 16);
+  const int64_t table_at = comp_bytes;
+  const int64_t dec_at = align16(table_at + nblk * (int64_t)sizeof(int64_t));
+  const int64_t full16 = align16(full);
+  for (int64_t i = 0; i < nblk; i++) {
+    out_off[i] = dec_at + i * full16;
+    blk_off[i] = deflate ? out_off[i] : in_off[i];
+  }
+  const int64_t total = deflate ? dec_at + nblk * full16 : dec_at;
+  DecodeBuffers B;
+  if (hipHostMalloc((void **)&B.pinned, (size_t)dec_at, hipHostMallocDefault) != hipSuccess) return GSKYHIP_E_HIP;
+  for (int64_t i = 0; i < nblk; i++) std::memcpy(B.pinned + in_off[i], &t.buf[d.offsets[plane0 + i]], (size_t)in_len[i]);
+  std::memcpy(B.pinned + table_at, blk_off.data(), (size_t)nblk * sizeof(int64_t));
+  if (hipMalloc((void **)&B.dev, (size_t)total) != hipSuccess) return GSKYHIP_E_HIP;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpyAsync(B.dev, B.pinned, (size_t)dec_at, hipMemcpyHostToDevice, s) != hipSuccess) return GSKYHIP_E_HIP;
+  int64_t decoded = 0;
+  if (deflate) {
+    std::vector<int32_t> status(nblk);
+    std::vector<int64_t> out_len(nblk);
+    const int rc = gskyhip_inflate_blocks(B.dev, in_off.data(), in_len.data(), (int)nblk, B.dev, out_off.data(),
+                                          out_cap.data(), out_need.data(), 1, status.data(), out_len.data(), stream);
+    if (rc) return rc;
+    for (int64_t i = 0; i < nblk; i++) {
+      if (status[i] != GSKYHIP_INFLATE_OK) return GSKYHIP_E_TYPE;   // what the host path returns for an undecodable block
+      decoded += out_len[i];
+    }
+  } else {
+    for (int64_t i = 0; i < nblk; i++) decoded += out_need[i];
+  }
+  const int64_t *dev_table = (const int64_t *)(B.dev + table_at);
+  const bool swap = t.be && bytes > 1 && d.predictor != 3;
+  if (swap || d.predictor == 2 || d.predictor == 3) {
+    const dim3 grid((unsigned)(nblk * L.bh)), blk(64);
+    if (nblk * L.bh > 0x7FFFFFFFll) return GSKYHIP_E_TYPE;
+    const int scan = d.predictor == 2 || d.predictor == 3;
+    const int64_t n = L.bw * L.samples;
+    if (d.predictor == 3 || bytes == 1)
+      hipLaunchKernelGGL(unpredict_kernel<uint8_t>, grid, blk, 0, s, B.dev, dev_table, nblk, L.bh, L.across, d.height,
+                         (int)d.tiled, row_bytes, d.predictor == 3 ? row_bytes : n, L.samples, 0, scan);
+    else if (bytes == 2)
+      hipLaunchKernelGGL(unpredict_kernel<uint16_t>, grid, blk, 0, s, B.dev, dev_table, nblk, L.bh, L.across, d.height,
+                         (int)d.tiled, row_bytes, n, L.samples, (int)swap, scan);
+    else if (bytes == 4)
+      hipLaunchKernelGGL(unpredict_kernel<uint32_t>, grid, blk, 0, s, B.dev, dev_table, nblk, L.bh, L.across, d.height,
+                         (int)d.tiled, row_bytes, n, L.samples, (int)swap, scan);
+    else
+      hipLaunchKernelGGL(unpredict_kernel<uint64_t>, grid, blk, 0, s, B.dev, dev_table, nblk, L.bh, L.across, d.height,
+                         (int)d.tiled, row_bytes, n, L.samples, (int)swap, scan);
+    if (hipGetLastError() != hipSuccess) return GSKYHIP_E_HIP;
+  }
+  {
+    const dim3 grid((unsigned)((npix + 255) / 256)), blk(256);
+    const int sample = L.samples == 1 ? 0 : band - 1, planes = d.predictor == 3;
+    switch (bytes) {
+      case 1: hipLaunchKernelGGL(place_tiff_kernel<uint8_t>, grid, blk, 0, s, B.dev, dev_table, (uint8_t *)dev_out, d.width, d.height, L.bw, L.bh, L.across, L.samples, sample, planes); break;
+      case 2: hipLaunchKernelGGL(place_tiff_kernel<uint16_t>, grid, blk, 0, s, B.dev, dev_table, (uint16_t *)dev_out, d.width, d.height, L.bw, L.bh, L.across, L.samples, sample, planes); break;
+      case 4: hipLaunchKernelGGL(place_tiff_kernel<uint32_t>, grid, blk, 0, s, B.dev, dev_table, (uint32_t *)dev_out, d.width, d.height, L.bw, L.bh, L.across, L.samples, sample, planes); break;
+      default: hipLaunchKernelGGL(place_tiff_kernel<uint64_t>, grid, blk, 0, s, B.dev, dev_table, (uint64_t *)dev_out, d.width, d.height, L.bw, L.bh, L.across, L.samples, sample, planes); break;
+    }
+    if (hipGetLastError() != hipSuccess) return GSKYHIP_E_HIP;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess) return GSKYHIP_E_HIP;   // the buffers are freed on return
+  if (stats) { stats[0] = nblk; stats[1] = 0; stats[2] = moved; stats[3] = decoded; }
+  return 0;
+}
+
+}  // namespace
+}  // namespace gsky
+
+static int geotiff_read_decode_impl(const char *path, int band, int level, void *dev_out, int64_t out_bytes, int decode,
+                                    int64_t *stats, void *stream) {
+  if (decode != GSKYHIP_DECODE_HOST && decode != GSKYHIP_DECODE_DEVICE) return GSKYHIP_E_ARG;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  Tiff t;
+  const Ifd *d = nullptr;
+  int rc = open_level(path, band, level, t, d);
+  if (rc) return rc;
+  const bool on_device = decode == GSKYHIP_DECODE_DEVICE &&
+                         (d->compression == 1 || d->compression == 8 || d->compression == 32946);
+  if (on_device) return geotiff_read_device(t, *d, band, dev_out, out_bytes, stats, stream);
+  rc = geotiff_read_opened(t, d, band, dev_out, out_bytes, stream);
+  if (!rc && stats) {
+    const Layout L = layout_of(*d);
+    stats[1] = L.across * L.down;
+    stats[3] = d->width * d->height * (d->bits / 8);
+  }
+  return rc;
+}
+
+extern "C" int gskyhip_geotiff_read_decode(const char *path, int band, int level, void *dev_out, int64_t out_bytes,
+                                           int decode, int64_t *stats, void *stream) {
+  try {
+    return geotiff_read_decode_impl(path, band, level, dev_out, out_bytes, decode, stats, stream);
   } catch (...) {   // a malformed file (bad_alloc of a size it declares): never through the C ABI
     return GSKYHIP_E_TYPE;
   }
@@ -1402,10 +1694,9 @@ extern "C" int gskyhip_netcdf_read_host(const char *path, int band, void *out, i
   }
 }
 
-static int netcdf_read_impl(const char *path, int band, void *dev_out, int64_t out_bytes, void *stream) {
-  NcRaster r;
-  int rc = nc_open_raster(path, r);
-  if (rc) return rc;
+// The host-decode device read of an opened file (gskyhip_netcdf_read).
+static int netcdf_read_opened(const NcRaster &r, int band, void *dev_out, int64_t out_bytes, void *stream) {
+  int rc = 0;
   if (band < 1 || band > r.nb) return 2;
   const int ts = nc_type_size(r.v->type);
   const int64_t n = r.nx * r.ny;
@@ -1428,9 +1719,182 @@ static int netcdf_read_impl(const char *path, int band, void *dev_out, int64_t o
   return rc;
 }
 
+static int netcdf_read_impl(const char *path, int band, void *dev_out, int64_t out_bytes, void *stream) {
+  NcRaster r;
+  const int rc = nc_open_raster(path, r);
+  return rc ? rc : netcdf_read_opened(r, band, dev_out, out_bytes, stream);
+}
+
 extern "C" int gskyhip_netcdf_read(const char *path, int band, void *dev_out, int64_t out_bytes, void *stream) {
   try {
     return netcdf_read_impl(path, band, dev_out, out_bytes, stream);
+  } catch (...) {   // a malformed file (bad_alloc of a size it declares): never through the C ABI
+    return GSKYHIP_E_TYPE;
+  }
+}
+
+// ======================================================================== netCDF-4 device decode
+namespace gsky {
+namespace {
+
+// Position of filter `id` in the pipeline, -1 when absent.
+int filter_at(const h5::Var &h, int id) {
+  for (int i = 0; i < (int)h.filters.size(); i++)
+    if (h.filters[i].id == id) return i;
+  return -1;
+}
+
+// The band's plane with the chunk decode on the device.  *fallback = true
+// (nothing done) when the variable is outside the device path.
+int netcdf_read_device(const NcRaster &r, int band, void *dev_out, int64_t *stats, void *stream, bool *fallback) {
+  *fallback = true;
+  if (r.v->h5v < 0) return 0;   // netCDF classic
+  const h5::Var &h = r.f.h5.vars[r.v->h5v];
+  const int ts = nc_type_size(r.v->type);
+  const int rank = (int)h.shape.size();
+  if (h.layout != 2 || (rank != 2 && rank != 3) || h.esize != ts || (int)h.chunk.size() != rank) return 0;
+  // the filter pipeline: nothing, shuffle, deflate, or shuffle then deflate (netCDF-C's order)
+  const int nf = (int)h.filters.size();
+  const int fs = filter_at(h, 2), fd = filter_at(h, 1);
+  if (!((nf == 0) || (nf == 1 && (fs == 0 || fd == 0)) || (nf == 2 && fs == 0 && fd == 1))) return 0;
+  if (fs >= 0 && !h.filters[fs].cd.empty() && (int)h.filters[fs].cd[0] != ts) return 0;
+  const uint64_t plane = (uint64_t)r.nx * r.ny;
+  std::vector<h5::ChunkInfo> list;
+  if (!h5::chunks(r.f.h5, h, (uint64_t)(band - 1) * plane, plane, list)) return 0;   // the host path reports it
+  const int64_t cy = (int64_t)h.chunk[rank - 2], cx = (int64_t)h.chunk[rank - 1];
+  const int64_t c0 = rank == 3 ? (int64_t)h.chunk[0] : 1;
+  const int64_t ncy = (r.ny + cy - 1) / cy, ncx = (r.nx + cx - 1) / cx;
+  if ((int64_t)list.size() != ncy * ncx || c0 > (1ll << 30) / std::max<int64_t>(1, cy * cx)) return 0;
+  const int64_t ne = c0 * cy * cx, cbytes = ne * ts;
+  const int64_t n = (int64_t)list.size();
+  std::vector<int64_t> in_off, in_len, out_off, out_cap, chunk_off(n, -1);
+  std::vector<int> inflated;   // chunk index per inflate job
+  std::vector<uint8_t> shuffled(n, 0);
+  int64_t at = 0, present = 0;
+  for (int64_t k = 0; k < n; k++) {
+    const h5::ChunkInfo &c = list[k];
+    if (!c.present) continue;
+    const bool defl = fd >= 0 && !(c.mask & (1u << fd));
+    const bool shuf = fs >= 0 && !(c.mask & (1u << fs)) && ts > 1;
+    // a stored chunk of another size than the chunk's own: the host path decides
+    if (!defl && ((int64_t)c.size < cbytes || (shuf && (int64_t)c.size != cbytes))) return 0;
+    if (defl && c.size > 0xFFFFFFFFull) return 0;
+    present++;
+    shuffled[k] = shuf ? 1 : 0;
+    const int64_t len = defl ? (int64_t)c.size : cbytes;
+    if (defl) {
+      inflated.push_back((int)k);
+      in_off.push_back(at);
+      in_len.push_back(len);
+    } else {
+      chunk_off[k] = at;
+    }
+    at = align16(at + len);
+  }
+  *fallback = false;
+  const int64_t comp_bytes = std::max<int64_t>(at, 16);
+  const int64_t table_at = comp_bytes;
+  const int64_t flags_at = table_at + n * (int64_t)sizeof(int64_t);
+  const int64_t dec_at = align16(flags_at + n);
+  const int64_t c16 = align16(cbytes);
+  for (size_t j = 0; j < inflated.size(); j++) {
+    out_off.push_back(dec_at + (int64_t)j * c16);
+    out_cap.push_back(cbytes);
+    chunk_off[inflated[j]] = out_off.back();
+  }
+  const int64_t total = dec_at + (int64_t)inflated.size() * c16;
+  DecodeBuffers B;
+  if (hipHostMalloc((void **)&B.pinned, (size_t)dec_at, hipHostMallocDefault) != hipSuccess) return GSKYHIP_E_HIP;
+  {
+    int64_t w = 0;   // the same walk as above
+    int64_t moved = 0;
+    for (int64_t k = 0; k < n; k++) {
+      const h5::ChunkInfo &c = list[k];
+      if (!c.present) continue;
+      const bool defl = fd >= 0 && !(c.mask & (1u << fd));
+      const int64_t len = defl ? (int64_t)c.size : cbytes;
+      std::memcpy(B.pinned + w, &r.f.h5.buf[c.addr], (size_t)len);
+      w = align16(w + len);
+      moved += len;
+    }
+    if (stats) stats[2] = moved;
+  }
+  std::memcpy(B.pinned + table_at, chunk_off.data(), (size_t)n * sizeof(int64_t));
+  std::memcpy(B.pinned + flags_at, shuffled.data(), (size_t)n);
+  if (hipMalloc((void **)&B.dev, (size_t)total) != hipSuccess) return GSKYHIP_E_HIP;
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemcpyAsync(B.dev, B.pinned, (size_t)dec_at, hipMemcpyHostToDevice, s) != hipSuccess) return GSKYHIP_E_HIP;
+  if (!inflated.empty()) {
+    std::vector<int32_t> status(inflated.size());
+    std::vector<int64_t> out_len(inflated.size());
+    const int rc = gskyhip_inflate_blocks(B.dev, in_off.data(), in_len.data(), (int)inflated.size(), B.dev,
+                                          out_off.data(), out_cap.data(), out_cap.data(), 1, status.data(),
+                                          out_len.data(), stream);
+    if (rc) return rc;
+    for (int32_t st : status)
+      if (st != GSKYHIP_INFLATE_OK) return GSKYHIP_E_ARG;   // what the host path returns for a chunk it cannot read
+  }
+  uint64_t fill = 0;
+  {
+    const std::vector<uint8_t> fb = h5::fill_value(h);
+    if ((int)fb.size() == ts) std::memcpy(&fill, fb.data(), (size_t)ts);   // file order, swapped with the data
+  }
+  const int64_t npix = r.nx * r.ny;
+  const int64_t lead = rank == 3 ? (int64_t)(band - 1) % c0 : 0;
+  const int swap = h.big_endian && ts > 1;
+  const dim3 grid((unsigned)((npix + 255) / 256)), blk(256);
+  const int64_t *dev_table = (const int64_t *)(B.dev + table_at);
+  const uint8_t *dev_flags = B.dev + flags_at;
+  switch (ts) {
+    case 1: hipLaunchKernelGGL(place_nc_kernel<uint8_t>, grid, blk, 0, s, B.dev, dev_table, dev_flags, (uint8_t *)dev_out, r.nx, r.ny, cy, cx, ncx, lead, ne, (int)r.bottom_up, swap, (uint8_t)fill); break;
+    case 2: hipLaunchKernelGGL(place_nc_kernel<uint16_t>, grid, blk, 0, s, B.dev, dev_table, dev_flags, (uint16_t *)dev_out, r.nx, r.ny, cy, cx, ncx, lead, ne, (int)r.bottom_up, swap, (uint16_t)fill); break;
+    case 4: hipLaunchKernelGGL(place_nc_kernel<uint32_t>, grid, blk, 0, s, B.dev, dev_table, dev_flags, (uint32_t *)dev_out, r.nx, r.ny, cy, cx, ncx, lead, ne, (int)r.bottom_up, swap, (uint32_t)fill); break;
+    default: hipLaunchKernelGGL(place_nc_kernel<uint64_t>, grid, blk, 0, s, B.dev, dev_table, dev_flags, (uint64_t *)dev_out, r.nx, r.ny, cy, cx, ncx, lead, ne, (int)r.bottom_up, swap, (uint64_t)fill); break;
+  }
+  if (hipGetLastError() != hipSuccess) return GSKYHIP_E_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess) return GSKYHIP_E_HIP;   // the buffers are freed on return
+  if (stats) { stats[0] = present; stats[1] = 0; stats[3] = present * cbytes; }
+  return 0;
+}
+
+}  // namespace
+}  // namespace gsky
+
+static int netcdf_read_decode_impl(const char *path, int band, void *dev_out, int64_t out_bytes, int decode,
+                                   int64_t *stats, void *stream) {
+  if (decode != GSKYHIP_DECODE_HOST && decode != GSKYHIP_DECODE_DEVICE) return GSKYHIP_E_ARG;
+  if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+  NcRaster r;
+  int rc = nc_open_raster(path, r);
+  if (rc) return rc;
+  const int ts = nc_type_size(r.v->type);
+  const int64_t n = r.nx * r.ny;
+  // a band or an output size the host read refuses is left to it, with its codes
+  const bool args_ok = band >= 1 && band <= r.nb && dev_out && out_bytes >= n * ts;
+  if (decode == GSKYHIP_DECODE_DEVICE && args_ok) {
+    bool fallback = true;
+    rc = netcdf_read_device(r, band, dev_out, stats, stream, &fallback);
+    if (!fallback || rc) return rc;
+  }
+  int64_t n_chunks = 1;   // the host path: a chunked variable's chunks, else the one piece
+  if (stats && args_ok && r.v->h5v >= 0 && r.f.h5.vars[r.v->h5v].layout == 2) {
+    std::vector<h5::ChunkInfo> list;
+    if (h5::chunks(r.f.h5, r.f.h5.vars[r.v->h5v], (uint64_t)(band - 1) * (uint64_t)n, (uint64_t)n, list))
+      n_chunks = (int64_t)list.size();
+  }
+  rc = netcdf_read_opened(r, band, dev_out, out_bytes, stream);
+  if (!rc && stats) {
+    stats[0] = stats[2] = 0;
+    stats[1] = n_chunks;
+    stats[3] = n * ts;
+  }
+  return rc;
+}
+
+extern "C" int gskyhip_netcdf_read_decode(const char *path, int band, void *dev_out, int64_t out_bytes, int decode,
+                                          int64_t *stats, void *stream) {
+  try {
+    return netcdf_read_decode_impl(path, band, dev_out, out_bytes, decode, stats, stream);
   } catch (...) {   // a malformed file (bad_alloc of a size it declares): never through the C ABI
     return GSKYHIP_E_TYPE;
   }

@@ -291,6 +291,62 @@ int gskyhip_build_overviews(const void *src, int dtype, int signed_byte, int xsi
 int gskyhip_register_geotiff_ovr(const char *path, int band, int method, int min_size);
 int gskyhip_register_netcdf_ovr(const char *path, int band, int method, int min_size);
 
+/* ---- Deflate decoded on the GPU; ingest with device-side block decode ----- */
+/* Per-block status of gskyhip_inflate_blocks (RFC 1950 / 1951 streams). */
+#define GSKYHIP_INFLATE_OK 0
+#define GSKYHIP_INFLATE_E_INPUT 1     /* input truncated                          */
+#define GSKYHIP_INFLATE_E_BLOCK 2     /* bad block type or header                 */
+#define GSKYHIP_INFLATE_E_CODES 3     /* bad code lengths / invalid code          */
+#define GSKYHIP_INFLATE_E_DIST 4      /* distance before the start of the output  */
+#define GSKYHIP_INFLATE_E_CAP 5       /* output capacity exceeded                 */
+#define GSKYHIP_INFLATE_E_CHECKSUM 6  /* Adler-32 mismatch                        */
+#define GSKYHIP_INFLATE_E_SHORT 7     /* output shorter than required             */
+/* n_blocks independent streams, one wave64 each: block k reads
+ * dev_in[in_off[k] .. + in_len[k]) and writes dev_out[out_off[k] .. ) with at
+ * most out_cap[k] bytes; fewer than out_need[k] (<= out_cap[k]) bytes is
+ * GSKYHIP_INFLATE_E_SHORT.  zlib_wrapper: 1 -- RFC 1950 header and Adler-32
+ * (verified); 0 -- a raw RFC 1951 stream.  The five offset / length arrays and
+ * status / out_len (n_blocks each) are HOST memory; in_len[k] < 2^32.  No byte
+ * outside a block's ranges is read or written whatever the stream holds; out
+ * bytes past out_len[k], and all of them when status[k] != 0, are unspecified.
+ * Returns GSKYHIP_OK once the launch has completed (the call waits for
+ * `stream`); per-block results are in status[].  The _host twin runs the same
+ * decoder (csrc/inflate_core.h) on up to 16 host threads over host pointers. */
+int gskyhip_inflate_blocks(const uint8_t *dev_in, const int64_t *in_off, const int64_t *in_len, int n_blocks,
+                           uint8_t *dev_out, const int64_t *out_off, const int64_t *out_cap,
+                           const int64_t *out_need, int zlib_wrapper, int32_t *status, int64_t *out_len,
+                           void *stream);
+int gskyhip_inflate_blocks_host(const uint8_t *in, const int64_t *in_off, const int64_t *in_len, int n_blocks,
+                                uint8_t *out, const int64_t *out_off, const int64_t *out_cap,
+                                const int64_t *out_need, int zlib_wrapper, int32_t *status, int64_t *out_len);
+/* gskyhip_geotiff_read / gskyhip_netcdf_read with the block decode on the
+ * device.  decode = GSKYHIP_DECODE_HOST is exactly the call without _decode.
+ * GSKYHIP_DECODE_DEVICE: the band's *compressed* blocks go to HBM in one copy,
+ * are inflated there (gskyhip_inflate_blocks), un-predicted / un-shuffled /
+ * byte-swapped and placed row-major by kernels.  GeoTIFF: compression 1, 8 and
+ * 32946, every layout and predictor the host path reads; LZW and PackBits
+ * files take the host path inside the same call.  netCDF-4: chunked variables
+ * whose filters are a subset of {shuffle, deflate} in that order; anything
+ * else (fletcher32, contiguous, compact, netCDF classic) takes the host path.
+ * stats (HOST int64[4], or NULL) = {blocks decoded on the device, blocks
+ * decoded on the host, compressed bytes copied to the device, decoded bytes
+ * produced}.  The result is bit-identical to the host decode; a block whose
+ * stream does not decode gives the host path's error (GSKYHIP_E_TYPE for a
+ * GeoTIFF, GSKYHIP_E_ARG for netCDF), dev_out then unspecified. */
+#define GSKYHIP_DECODE_HOST 0
+#define GSKYHIP_DECODE_DEVICE 1
+int gskyhip_geotiff_read_decode(const char *path, int band, int level, void *dev_out, int64_t out_bytes, int decode,
+                                int64_t *stats, void *stream);
+int gskyhip_netcdf_read_decode(const char *path, int band, void *dev_out, int64_t out_bytes, int decode,
+                               int64_t *stats, void *stream);
+/* gskyhip_register_geotiff[_ovr] / _netcdf[_ovr] with every level read
+ * through the _decode call above; ovr_method -1: no pyramid is built.  The
+ * decode mode is remembered like the pyramid request: the drop-in uses it
+ * when it reads the file again (changed on disk, or evicted), until the file
+ * is registered through another call. */
+int gskyhip_register_geotiff_decode(const char *path, int band, int ovr_method, int min_size, int decode);
+int gskyhip_register_netcdf_decode(const char *path, int band, int ovr_method, int min_size, int decode);
+
 /* ---- drop-in for the cgo entry point of the worker ----------------------- */
 /* Registers an HBM-resident granule under (path, band) so that the drop-in
  * below can find it (it replaces GDALOpenEx in warp.go:89-101; GeoTIFF files
