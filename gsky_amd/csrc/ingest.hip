@@ -65,6 +65,7 @@
 #include <vector>
 
 #include "../../include/gskyhip.h"
+#include "crs.h"
 #include "hdf5.h"
 
 namespace gsky {
@@ -1200,6 +1201,26 @@ int nc_open_raster(const char *path, NcRaster &r) {
   return 0;
 }
 
+// The variable that v's grid_mapping attribute names (the attribute's text up
+// to its first NUL: text attributes may carry one), or null.
+const NcVar *nc_grid_mapping_var(const Nc &f, const NcVar &v) {
+  const NcAtt *gm = nc_att(v.atts, "grid_mapping");
+  if (!gm) return nullptr;
+  for (const NcVar &m : f.vars)
+    if (m.name == gm->text.c_str()) return &m;
+  return nullptr;
+}
+
+// True when v's last two dimensions are named as longitude / latitude axes
+// (x with lat, or lon with y, counts; x with y does not): EPSG:4326 then.
+bool nc_lonlat_axes(const Nc &f, const NcVar &v) {
+  const size_t nd = v.dims.size();
+  auto low = [](std::string s) { for (auto &ch : s) ch = (char)std::tolower((unsigned char)ch); return s; };
+  const std::string x = low(f.dims[v.dims[nd - 1]].first), y = low(f.dims[v.dims[nd - 2]].first);
+  return (x == "lon" || x == "longitude" || x == "x") && (y == "lat" || y == "latitude" || y == "y") &&
+         (x != "x" || y != "y");
+}
+
 // bIsGdalFile of the driver (netcdfdataset.cpp:2498-2518): a global "GDAL"
 // attribute of version >= 1.9 (NCDFIsGDALVersionGTE, 8879-8919), or
 // spatial_ref + GeoTransform on the variable's grid_mapping variable.
@@ -1232,11 +1253,8 @@ bool nc_is_gdal_file(const Nc &f, const NcVar &v) {
       if (1900 <= vn) return true;
     }
   }
-  if (const NcAtt *gm = nc_att(v.atts, "grid_mapping"))
-    for (const NcVar &m : f.vars)
-      if (m.name == std::string(gm->text.c_str()) && nc_att(m.atts, "spatial_ref") && nc_att(m.atts, "GeoTransform"))
-        return true;
-  return false;
+  const NcVar *m = nc_grid_mapping_var(f, v);
+  return m && nc_att(m->atts, "spatial_ref") && nc_att(m->atts, "GeoTransform");
 }
 
 // Data type, signedness and nodata of a variable as netCDFRasterBand sets
@@ -1298,25 +1316,21 @@ int nc_dtype(const Nc &f, const NcVar &v, int &signed_byte, double &nodata) {
   }
 }
 
+// The EPSG code that the GDAL-written WKT of the grid mapping variable names
+// (crs_wkt, else spatial_ref), into *code; false without one.
+bool nc_wkt_epsg(const Nc &f, const NcVar &v, int *code) {
+  if (const NcVar *m = nc_grid_mapping_var(f, v))
+    for (const char *k : {"crs_wkt", "spatial_ref"}) {
+      const NcAtt *w = nc_att(m->atts, k);
+      if (w && wkt_epsg_code(w->text, code)) return true;
+    }
+  return false;
+}
+
 int nc_epsg(const Nc &f, const NcVar &v) {
-  const NcAtt *gm = nc_att(v.atts, "grid_mapping");
-  if (gm)
-    for (const NcVar &m : f.vars)
-      if (m.name == std::string(gm->text.c_str()))   // text attributes may carry a NUL
-        for (const char *k : {"crs_wkt", "spatial_ref"}) {
-          const NcAtt *w = nc_att(m.atts, k);
-          if (!w) continue;
-          const size_t a = w->text.rfind("AUTHORITY[\"EPSG\",\"");
-          if (a != std::string::npos) return std::atoi(w->text.c_str() + a + 18);
-        }
-  const size_t nd = v.dims.size();
-  const std::string &xn = f.dims[v.dims[nd - 1]].first, &yn = f.dims[v.dims[nd - 2]].first;
-  auto low = [](std::string s) { for (auto &ch : s) ch = (char)std::tolower((unsigned char)ch); return s; };
-  const std::string x = low(xn), y = low(yn);
-  if ((x == "lon" || x == "longitude" || x == "x") && (y == "lat" || y == "latitude" || y == "y") &&
-      (x != "x" || y != "y"))
-    return 4326;
-  return 0;
+  int code;
+  if (nc_wkt_epsg(f, v, &code)) return code;
+  return nc_lonlat_axes(f, v) ? 4326 : 0;
 }
 
 // perspective_point_height where the CF geostationary mapping omits it
@@ -1326,17 +1340,12 @@ constexpr double kGeosDefaultH = 35785831.0;
 // True, with the satellite height, when the variable's grid mapping is the CF
 // geostationary one: its x / y axes may then be scan angles (nc_fill_info).
 bool nc_geos_height(const Nc &f, const NcVar &v, double &h) {
-  const NcAtt *gm = nc_att(v.atts, "grid_mapping");
-  if (!gm) return false;
-  for (const NcVar &m : f.vars) {
-    if (m.name != std::string(gm->text.c_str())) continue;
-    const NcAtt *gn = nc_att(m.atts, "grid_mapping_name");
-    if (!gn || strcasecmp(gn->text.c_str(), "geostationary") != 0) return false;
-    const NcAtt *a = nc_att(m.atts, "perspective_point_height");
-    h = (a && !a->num.empty()) ? a->num[0] : kGeosDefaultH;
-    return true;
-  }
-  return false;
+  const NcVar *m = nc_grid_mapping_var(f, v);
+  const NcAtt *gn = m ? nc_att(m->atts, "grid_mapping_name") : nullptr;
+  if (!gn || strcasecmp(gn->text.c_str(), "geostationary") != 0) return false;
+  const NcAtt *a = nc_att(m->atts, "perspective_point_height");
+  h = (a && !a->num.empty()) ? a->num[0] : kGeosDefaultH;
+  return true;
 }
 
 // The SRS of the variable's CF grid mapping (grid_mapping_name and its
@@ -1354,11 +1363,9 @@ std::string nc_cf_srs(const Nc &f, const NcVar &v) {
     const NcAtt *a = nc_att(m.atts, k);
     return a && !a->num.empty();
   };
-  if (const NcAtt *gm = nc_att(v.atts, "grid_mapping"))
-    for (const NcVar &m : f.vars) {
-      if (m.name != std::string(gm->text.c_str())) continue;
-      const NcAtt *gn = nc_att(m.atts, "grid_mapping_name");
-      if (!gn) break;
+  if (const NcVar *mp = nc_grid_mapping_var(f, v))
+    if (const NcAtt *gn = nc_att(mp->atts, "grid_mapping_name")) {   // (without the name: the axis rule below)
+      const NcVar &m = *mp;
       std::string name(gn->text.c_str());
       for (auto &ch : name) ch = (char)std::tolower((unsigned char)ch);
       // the ellipsoid: earth_radius, else semi_major_axis with
@@ -1480,13 +1487,7 @@ std::string nc_cf_srs(const Nc &f, const NcVar &v) {
       }
       return "?";
     }
-  const size_t nd = v.dims.size();
-  auto low = [](std::string s) { for (auto &ch : s) ch = (char)std::tolower((unsigned char)ch); return s; };
-  const std::string x = low(f.dims[v.dims[nd - 1]].first), y = low(f.dims[v.dims[nd - 2]].first);
-  if ((x == "lon" || x == "longitude" || x == "x") && (y == "lat" || y == "latitude" || y == "y") &&
-      (x != "x" || y != "y"))
-    return "EPSG:4326";
-  return "";
+  return nc_lonlat_axes(f, v) ? "EPSG:4326" : "";
 }
 
 // The dataset SRS for the srs_cf open option (netcdfdataset.cpp:7023-7025,
@@ -1494,16 +1495,8 @@ std::string nc_cf_srs(const Nc &f, const NcVar &v) {
 // the grid mapping wins when it names an EPSG code, else the CF mapping;
 // srs_cf=yes -- the CF mapping only.
 std::string nc_srs(const Nc &f, const NcVar &v, bool srs_cf) {
-  if (!srs_cf)
-    if (const NcAtt *gm = nc_att(v.atts, "grid_mapping"))
-      for (const NcVar &m : f.vars)
-        if (m.name == std::string(gm->text.c_str()))
-          for (const char *k : {"crs_wkt", "spatial_ref"}) {
-            const NcAtt *w = nc_att(m.atts, k);
-            if (!w) continue;
-            const size_t a = w->text.rfind("AUTHORITY[\"EPSG\",\"");
-            if (a != std::string::npos) return "EPSG:" + std::to_string(std::atoi(w->text.c_str() + a + 18));
-          }
+  int code;
+  if (!srs_cf && nc_wkt_epsg(f, v, &code)) return "EPSG:" + std::to_string(code);
   return nc_cf_srs(f, v);
 }
 
