@@ -25,6 +25,7 @@ CRS_TMERC, CRS_LCC, CRS_STERE_POLAR, CRS_GEOS, CRS_LAEA, CRS_CEA, CRS_MERC = 4, 
 RESAMPLE_NEAREST, RESAMPLE_BILINEAR = 0, 1
 RESAMPLE_CUBIC = 2
 RESAMPLE_AVERAGE, RESAMPLE_MODE = 3, 4   # the area rules (include/gskyhip.h)
+RESAMPLE_CUBICSPLINE, RESAMPLE_LANCZOS = 5, 6   # the point kernels: cubic B-spline, Lanczos (a = 3)
 # value-type hint bits of gskyhip_render_tiles_typed
 VT_BIT = {BYTE: 1, SIGNEDBYTE: 2, INT16: 4, UINT16: 8, FLOAT32: 16}
 MAX_OVR = 12

@@ -134,8 +134,8 @@ def gather_coverage(band, extents: Sequence[Tuple[int, int]], height: int, width
 
 def render_band_gpu(cfg, chunks: Sequence[Chunk], rows: Tuple[int, int], width: int, device, out=None):
     """Renders the chunks of chunk rows [rows) of a synth-style coverage config
-    on `device` (one namespace, Float32 canvases, cfg.resample) and returns the
-    (band rows, width) band.  Only granules intersecting the band's chunks are
+    on `device` (one namespace, Float32 canvases, cfg.resample: any of
+    _lib.RESAMPLE_*, 0..6) and returns the (band rows, width) band.  Only granules intersecting the band's chunks are
     uploaded.  `out`: a (band rows, width) float32 view to render into -- rank
     0 passes its rows of the coverage, so its band is never copied."""
     import numpy as np

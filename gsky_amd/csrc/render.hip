@@ -2149,7 +2149,7 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
                   const uint8_t *ramp, uint8_t *rgba_out, void *canvas_out, int phase) {
   if (n_out != 1 && n_out != 3) return GSKYHIP_E_ARG;  // ogc_encoders.go:135-136
   for (int k = 0; k < n_out; k++) if (out_ns[k] < 0 || out_ns[k] >= 4) return GSKYHIP_E_ARG;
-  if (rc.resample < GSKYHIP_RESAMPLE_NEAREST || rc.resample > GSKYHIP_RESAMPLE_MODE) return GSKYHIP_E_ARG;
+  if (rc.resample < GSKYHIP_RESAMPLE_NEAREST || rc.resample > GSKYHIP_RESAMPLE_LANCZOS) return GSKYHIP_E_ARG;
   // rgba_out == NULL: canvases only (WCS GetCoverage, FusionUnscale, ows.go:728)
   const bool autom = rgba_out && sp.offset == 0.0 && sp.scale == 0.0 && sp.clip == 0.0;
   if ((autom || !rgba_out) && !canvas_out) return GSKYHIP_E_ARG;
@@ -2208,6 +2208,10 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
     if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask) lds_mode = kCanvas | kAverage;
   } else if (rc.resample == GSKYHIP_RESAMPLE_MODE) {
     // mode: the generic kernels
+  } else if (is_kernel(rc.resample)) {
+    // spline, Lanczos: the same combination has render_kern_kernel (render_kern.h)
+    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask)
+      lds_mode = kCanvas | (rc.resample == GSKYHIP_RESAMPLE_LANCZOS ? kLanczos : kSpline);
   } else if (vt && n_out == 1 && !autom) {
     if (a.write_rgba && !canvas_out) lds_mode = bil ? kBilinear : 0;
     else if (!rgba_out && canvas_out) lds_mode = kCanvas | (bil ? kBilinear : 0);
@@ -2337,6 +2341,7 @@ int launch_warp_jobs(const RenderCall &rc, const BlockStatsJob *jobs, int64_t ma
 
 int launch_warp_windows(const RenderCall &rc, int32_t *bbox_out, int32_t *dtype_out, double *nodata_out,
                         void *win_out, int64_t win_stride) {
+  if (rc.resample < GSKYHIP_RESAMPLE_NEAREST || rc.resample > GSKYHIP_RESAMPLE_LANCZOS) return GSKYHIP_E_ARG;
   Carve cv;
   int rcode = plan_all(rc, cv);
   if (rcode || rc.n_pairs <= 0) return rcode;
@@ -2356,6 +2361,12 @@ int launch_warp_windows(const RenderCall &rc, int32_t *bbox_out, int32_t *dtype_
                        cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
   else if (rc.resample == GSKYHIP_RESAMPLE_MODE)
     hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_MODE>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
+                       cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
+  else if (rc.resample == GSKYHIP_RESAMPLE_CUBICSPLINE)
+    hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_CUBICSPLINE>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
+                       cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
+  else if (rc.resample == GSKYHIP_RESAMPLE_LANCZOS)
+    hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_LANCZOS>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,
                        cv.rows, cv.pool, rc.max_h, rc.max_w, rc.n_pairs, (uint8_t *)win_out, (long)win_stride);
   else
     hipLaunchKernelGGL(warp_window_kernel<GSKYHIP_RESAMPLE_NEAREST>, grid, dim3(256), 0, s, cv.pairs, cv.xforms,

@@ -207,7 +207,7 @@ struct RenderArgs {
   MinMax *minmax;        // n_tiles * 3
   int write_rgba;
   const EntryD *entries;
-  int lds_mode;          // typed band kernels: kBilinear | kCanvas | kCubic | kAverage bits of the call
+  int lds_mode;          // typed band kernels: kBilinear | kCanvas | kCubic | kAverage | kSpline | kLanczos bits of the call
   const int64_t *cov_offsets;  // canvas mode: per tile element offset into one image (NULL: slots)
   int64_t cov_stride;          // ... and that image's row stride (elements)
 };
@@ -330,6 +330,23 @@ __device__ __forceinline__ bool cub_fetch(const EntryD &e, double sx, double sy,
 template <typename T>
 __device__ __noinline__ bool cub_fetch_call(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
   return cub_fetch<T>(e, sx, sy, v);
+}
+
+// kernel_rule() (resample.h; RES the spline or Lanczos) of one window pixel in
+// type T, as cub_fetch(); the _call form for the generic kernels.
+template <typename T, int RES>
+__device__ __forceinline__ bool kern_fetch(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
+  const T *band = (const T *)e.band;
+  double r;
+  if (!kernel_rule<kernel_radius(RES)>(e.band_x, e.band_y, e.has_nodata, e.nodata64, sx, sy,
+                                       [&](int xx, int yy) { return bil_tap<T>(band[(long)yy * e.band_x + xx]); }, r))
+    return false;
+  v = resample_store<T>(r, e.out_dtype);
+  return true;
+}
+template <typename T, int RES>
+__device__ __noinline__ bool kern_fetch_call(const EntryD &e, double sx, double sy, typename VOf<T>::type &v) {
+  return kern_fetch<T, RES>(e, sx, sy, v);
 }
 
 // average_rule() / mode_rule() (resample.h; RES picks) of window pixel (ic, ir)
@@ -497,6 +514,7 @@ constexpr int kLdsBandRows = 16;   // rows per block of render_lds_kernel
 constexpr int kBilinear = 4, kCanvas = 8;   // render_lds_kernel modes (RenderArgs.lds_mode)
 constexpr int kCubic = 16;                  // float32 canvases by cubic convolution: render_cub_kernel (render_cub.h)
 constexpr int kAverage = 32;                // float32 canvases by area average: render_avg_kernel (render_area.h)
+constexpr int kSpline = 64, kLanczos = 128; // float32 canvases by a point kernel: render_kern_kernel (render_kern.h)
 
 // The typed band kernels (render_lds.hip) for value type `vt`.
 void launch_band_kernels(const RenderArgs &a, int vt, bool mask, int n_items, hipStream_t s);

@@ -65,6 +65,17 @@ __device__ __noinline__ Val cubic_value(const PairPlan &pp, double sx, double sy
   return resample_store(r, pp.out_dtype);
 }
 
+// kernel_rule() (resample.h) of a pair at (sx, sy), RES the spline or Lanczos.
+template <int RES>
+__device__ __noinline__ Val kernel_value(const PairPlan &pp, double sx, double sy) {
+  double r;
+  if (!kernel_rule<kernel_radius(RES)>(
+          pp.band_x, pp.band_y, pp.has_nodata, pp.nodata, sx, sy,
+          [&](int xx, int yy) { return load_dbl(pp.band, pp.src_dtype, (long)yy * pp.band_x + xx); }, r))
+    return pp.fill;
+  return resample_store(r, pp.out_dtype);
+}
+
 // average_rule() / mode_rule() (resample.h) of a pair over the footprint
 // (sx +- hx, sy +- hy), taps as above.
 __device__ __noinline__ Val average_value(const PairPlan &pp, double sx, double sy, double hx, double hy) {
@@ -108,10 +119,12 @@ __device__ __noinline__ void area_footprint(const PairPlan &pp, const RowRec &rr
 // source value or the window's nodata fill (warp.go:271-344).
 template <int RES>
 __device__ __forceinline__ Val sampled_value(const PairPlan &pp, double sx, double sy) {
-  static_assert(RES == GSKYHIP_RESAMPLE_NEAREST || RES == GSKYHIP_RESAMPLE_BILINEAR || RES == GSKYHIP_RESAMPLE_CUBIC,
+  static_assert(RES == GSKYHIP_RESAMPLE_NEAREST || RES == GSKYHIP_RESAMPLE_BILINEAR ||
+                    RES == GSKYHIP_RESAMPLE_CUBIC || is_kernel(RES),
                 "a resampling rule of resample.h");
   if (RES == GSKYHIP_RESAMPLE_BILINEAR) return bilinear_value(pp, sx, sy);
   if (RES == GSKYHIP_RESAMPLE_CUBIC) return cubic_value(pp, sx, sy);
+  if constexpr (is_kernel(RES)) return kernel_value<RES>(pp, sx, sy);
   long idx;
   if (!nn_index(sx, sy, pp.band_x, pp.band_y, idx)) return pp.fill;
   Val v = load_val(pp.band, pp.src_dtype, idx);
@@ -389,6 +402,10 @@ __device__ __forceinline__ void render_fast_t(const RenderArgs &a, const EntryD 
             v = fillv;
             V got;
             if (in && okq[q] && cub_fetch_call<T>(e, sx, sy, got)) v = got;
+          } else if constexpr (is_kernel(RES)) {
+            v = fillv;
+            V got;
+            if (in && okq[q] && kern_fetch_call<T, RES>(e, sx, sy, got)) v = got;
           } else if constexpr (is_area(RES)) {
             v = fillv;
             if (in && okq[q]) v = area_fetch<T, RES>(e, rows, pool, ic, ir, sx, sy, fillv);
@@ -539,6 +556,12 @@ static void dispatch_render_t(const RenderArgs &a, int resample, bool mask, dim3
   } else if (resample == GSKYHIP_RESAMPLE_MODE) {
     if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_MODE, true>(a, grid, general_only, s);
     else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_MODE, false>(a, grid, general_only, s);
+  } else if (resample == GSKYHIP_RESAMPLE_CUBICSPLINE) {
+    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBICSPLINE, true>(a, grid, general_only, s);
+    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBICSPLINE, false>(a, grid, general_only, s);
+  } else if (resample == GSKYHIP_RESAMPLE_LANCZOS) {
+    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_LANCZOS, true>(a, grid, general_only, s);
+    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_LANCZOS, false>(a, grid, general_only, s);
   } else {
     if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_NEAREST, true>(a, grid, general_only, s);
     else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_NEAREST, false>(a, grid, general_only, s);

@@ -944,10 +944,13 @@ void launch_bil(const RenderArgs &a, int n_items, hipStream_t s);   // render_bi
 void launch_cub(const RenderArgs &a, hipStream_t s);                // render_cub.h, band_f32.hip
 
 void launch_avg(const RenderArgs &a, hipStream_t s);                // render_area.h, band_f32.hip
+void launch_spline(const RenderArgs &a, hipStream_t s);             // render_kern.h, band_f32.hip
+void launch_lanczos(const RenderArgs &a, hipStream_t s);            // render_kern.h, band_f32.hip
 
 // Band kernel of one call: cubic float canvases -> render_cub_kernel, area
-// average float canvases -> render_avg_kernel (launch_render sets kCubic and
-// kAverage for float32 canvases without a mask layer only);
+// average float canvases -> render_avg_kernel, spline and Lanczos float
+// canvases -> render_kern_kernel (launch_render sets kCubic, kAverage, kSpline
+// and kLanczos for float32 canvases without a mask layer only);
 // bilinear float canvases without a mask layer -> render_bil_kernel; other
 // bilinear work -> render_lds_kernel; nearest neighbour -> render_nn_kernel.
 template <typename T>
@@ -958,6 +961,13 @@ void launch_band_t(const RenderArgs &a, bool mask, int n_items, hipStream_t s) {
   }
   if ((a.lds_mode & kAverage) != 0) {
     if constexpr (std::is_same<T, float>::value) launch_avg(a, s);
+    return;
+  }
+  if ((a.lds_mode & (kSpline | kLanczos)) != 0) {
+    if constexpr (std::is_same<T, float>::value) {
+      if ((a.lds_mode & kLanczos) != 0) launch_lanczos(a, s);
+      else launch_spline(a, s);
+    }
     return;
   }
   if ((a.lds_mode & kBilinear) != 0) {

@@ -1,6 +1,7 @@
 // resample.h -- the per-pixel resampling rules, each written once: the
 // nearest-neighbour index rule (warp.go:271-300), GWKBilinearResample4Sample
-// and GWKCubicResample4Sample (GDAL 3.0.1) in fp64, the area average and mode
+// and GWKCubicResample4Sample (GDAL 3.0.1) in fp64, the cubic B-spline and
+// Lanczos point kernels (after GWKResample), the area average and mode
 // over a pixel's footprint (after GWKAverageOrMode), the exit conversion to
 // the window's type, and the fp32 renormalised 2 x 2 of the float canvas
 // kernels.  The fp64 rules take a tap accessor `double tap(int xx, int yy)`,
@@ -119,6 +120,88 @@ __device__ __forceinline__ bool cubic_rule(int bx, int by, bool has_nodata, doub
   return true;
 }
 
+// ------------------------------------------------------- the point kernels
+// GSKYHIP_RESAMPLE_CUBICSPLINE / _LANCZOS (gskyhip.h), after GDAL's general
+// GWKResample at scale 1 with GWKBSpline / GWKLanczosSinc as the weights:
+// 2 R x 2 R taps around floor(s - 0.5), R = kernel_radius().
+constexpr bool is_kernel(int res) { return res == GSKYHIP_RESAMPLE_CUBICSPLINE || res == GSKYHIP_RESAMPLE_LANCZOS; }
+constexpr int kernel_radius(int res) { return res == GSKYHIP_RESAMPLE_LANCZOS ? 3 : 2; }
+
+// The cubic B-spline at x: >= 0, zero at and beyond 2, its integer samples
+// sum to 1.  Every operation in the written order (the numpy rule of
+// tests/test_kernel_rule.py evaluates the same sequence).
+__device__ __forceinline__ double bspline_weight(double x) {
+  const double a = fabs(x);
+  if (a < 1.0) {
+    const double a2 = a * a;
+    return ((4.0 - 6.0 * a2) + 3.0 * (a2 * a)) / 6.0;
+  }
+  if (a < 2.0) {
+    const double u = 2.0 - a;
+    return (u * u * u) / 6.0;
+  }
+  return 0.0;
+}
+
+// Lanczos, a = 3: sinc(x) sinc(x / 3), zero at and beyond 3.
+__device__ __forceinline__ double lanczos_weight(double x) {
+  if (x == 0.0) return 1.0;
+  if (fabs(x) >= 3.0) return 0.0;
+  const double p = M_PI * x;
+  const double q = p / 3.0;
+  return sin(p) * sin(q) / (p * q);
+}
+
+// The centre 2 x 2 of a point-kernel sample lies inside an nx x ny band
+// (tested on the floored doubles, cubic_inside()'s reason).
+__device__ __forceinline__ bool kernel_inside(double fx, double fy, int nx, int ny) {
+  return fx >= 0.0 && fx + 1.0 < (double)nx && fy >= 0.0 && fy + 1.0 < (double)ny;
+}
+
+// The rule of radius R (2: spline, 3: Lanczos).  The centre 2 x 2 must lie
+// inside the band and hold no nodata, else the pixel takes bilinear_rule();
+// an outer tap outside the band or holding the nodata is dropped and the
+// weights renormalised: w = wx * wy, accW += w, accR += d * w, rows outer,
+// always divided.  false -> no sample.
+template <int R, typename Tap>
+__device__ __forceinline__ bool kernel_rule(int bx, int by, bool has_nodata, double nodata64, double sx, double sy,
+                                            Tap tap, double &r) {
+  static_assert(R == 2 || R == 3, "spline or Lanczos");
+  const double fx = floor(sx - 0.5), fy = floor(sy - 0.5);
+  if (!kernel_inside(fx, fy, bx, by)) return bilinear_rule(bx, by, has_nodata, nodata64, sx, sy, tap, r);
+  const int iX = (int)fx, iY = (int)fy;
+  bool anynd = false;
+#pragma unroll
+  for (int k = 0; k < 4; k++) anynd = anynd || tap_is_nodata(tap(iX + (k & 1), iY + (k >> 1)), has_nodata, nodata64);
+  if (anynd) return bilinear_rule(bx, by, has_nodata, nodata64, sx, sy, tap, r);
+  const double tx = sx - 0.5 - fx, ty = sy - 0.5 - fy;
+  auto K = [](double x) { return R == 2 ? bspline_weight(x) : lanczos_weight(x); };
+  double wx[2 * R];
+#pragma unroll
+  for (int i = 0; i < 2 * R; i++) wx[i] = K((double)(i + 1 - R) - tx);
+  double accR = 0.0, accW = 0.0;
+  // rows rolled (a row's weight is made where it is used), columns unrolled:
+  // wx stays in registers and the body holds 2 R taps, not 4 R^2
+#pragma unroll 1
+  for (int j = 0; j < 2 * R; j++) {
+    const int yy = iY + 1 - R + j;
+    if (yy < 0 || yy >= by) continue;
+    const double wyj = K((double)(j + 1 - R) - ty);
+#pragma unroll
+    for (int i = 0; i < 2 * R; i++) {
+      const int xx = iX + 1 - R + i;
+      if (xx < 0 || xx >= bx) continue;
+      const double d = tap(xx, yy);
+      if (tap_is_nodata(d, has_nodata, nodata64)) continue;
+      const double w = wx[i] * wyj;
+      accW += w;
+      accR += d * w;
+    }
+  }
+  r = accR / accW;
+  return true;
+}
+
 // ---------------------------------------------------------------- area rules
 // GSKYHIP_RESAMPLE_AVERAGE / _MODE (gskyhip.h), after GDAL's GWKAverageOrMode:
 // a pixel's footprint in the source is the box [sx - hx, sx + hx] x [sy - hy,
@@ -129,9 +212,9 @@ constexpr int kAreaTaps = 8;   // taps per axis at the most (64 per pixel)
 
 constexpr bool is_area(int res) { return res == GSKYHIP_RESAMPLE_AVERAGE || res == GSKYHIP_RESAMPLE_MODE; }
 // The rule a raster of the mask layer warps by under the data's rule `res`:
-// nearest neighbour under the area rules (bit fields are neither averaged nor
-// voted), else the data's.
-constexpr int mask_res(int res) { return is_area(res) ? GSKYHIP_RESAMPLE_NEAREST : res; }
+// nearest neighbour under the area rules and the point kernels (bit fields
+// are neither averaged, voted nor convolved), else the data's.
+constexpr int mask_res(int res) { return (is_area(res) || is_kernel(res)) ? GSKYHIP_RESAMPLE_NEAREST : res; }
 
 // Half extent of a footprint along one axis from that axis' component of
 // u = S(i + 1, row) - S(i, row) and v = S(i, row + 1) - S(i, row).

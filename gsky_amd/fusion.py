@@ -48,7 +48,7 @@ class FusionLayer:
     effective dates); None: tiles without a granule are absent."""
     batch: "object"
     params: ScaleParams
-    resample: int = 0
+    resample: int = 0                  # _lib.RESAMPLE_*, 0..6, as TileBatch.render()
     present: Optional[Sequence[bool]] = None
 
     def render(self) -> LayerCanvases:

@@ -128,7 +128,7 @@ class SynthConfig:
     namespaces: List[str]
     scale: Tuple[float, float, float, int]   # offset, scale, clip, colour_scale
     palette: Optional[list]
-    resample: int = 0
+    resample: int = 0                        # _lib.RESAMPLE_*, 0..6 (5 cubic B-spline, 6 Lanczos)
     mask: Optional[dict] = None
     bbox: Optional[Tuple[float, float, float, float]] = None   # whole coverage (C3)
     out_w: int = 0

@@ -214,9 +214,10 @@ class TileBatch:
         tensor (n_tiles, H, W, 4); with canvas=True also the typed canvases
         (n_tiles, n_out, H*W*4 bytes).  rgba=False renders canvases only (WCS).
         resample: 0 nearest, 1 bilinear, 2 cubic convolution, 3 area average,
-        4 area mode (_lib.RESAMPLE_*; GDAL's 4-sample formulas and the area
-        rules modelled on GWKAverageOrMode, include/gskyhip.h).  Under 3 and 4
-        rasters of the mask layer warp by nearest neighbour.
+        4 area mode, 5 cubic B-spline, 6 Lanczos (_lib.RESAMPLE_*; GDAL's
+        4-sample formulas, the area rules modelled on GWKAverageOrMode and the
+        point kernels modelled on GWKResample, include/gskyhip.h).  Under 3 to
+        6 rasters of the mask layer warp by nearest neighbour.
         phase 1 / 2 run the planning / render kernels alone (same arguments)."""
         n_out = len(self.namespaces)
         if n_out not in (1, 3):
@@ -293,7 +294,7 @@ class TileBatch:
 
     def graph(self, params: ScaleParams, palette: Optional[Palette] = None, resample: int = 0) -> "RenderGraph":
         """The batch's render (planning + band kernels, RGBA out) captured as
-        one HIP graph (see RenderGraph).  resample: as render(), 0..4."""
+        one HIP graph (see RenderGraph).  resample: as render(), 0..6."""
         return RenderGraph(self, params, palette, resample)
 
     def render_coverage(self, params: ScaleParams, out: torch.Tensor, offsets, resample: int = 0,
@@ -303,8 +304,8 @@ class TileBatch:
         tile t's top-left at flat element offset offsets[t]
         (gskyhip_render_coverage; no per-tile slots, no assembly copy).
         resample: 0 nearest, 1 bilinear, 2 cubic convolution, 3 area average,
-        4 area mode; float32 coverages have a band kernel for 0..3, mode
-        runs the generic kernels."""
+        4 area mode, 5 cubic B-spline, 6 Lanczos; float32 coverages have a
+        band kernel for 0..3, 5 and 6, mode runs the generic kernels."""
         if out.dim() != 2:
             raise ValueError("coverage must be 2-D")
         offs = offsets if isinstance(offsets, torch.Tensor) else torch.tensor(list(offsets), dtype=torch.int64)
@@ -370,7 +371,7 @@ class TileBatch:
         """The FlexRasters of tile_grpc.go:228-241: per pair
         (window tensor, bbox [xoff, yoff, w, h], type name, nodata).
         resample: 0 nearest, 1 bilinear, 2 cubic convolution, 3 area average,
-        4 area mode."""
+        4 area mode, 5 cubic B-spline, 6 Lanczos."""
         npairs = self.n_pairs
         bbox = torch.zeros((max(1, npairs), 4), dtype=torch.int32, device=self.device)
         dt = torch.zeros(max(1, npairs), dtype=torch.int32, device=self.device)
@@ -452,7 +453,7 @@ class PipelinedBatch:
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """RGBA of every tile, (n_tiles, max_h, max_w, 4); ordered after the
         work already queued on the current stream, and the current stream
-        waits for every chunk."""
+        waits for every chunk.  resample: as TileBatch.render(), 0..6."""
         if out is None:
             if self._out is None:
                 self._out = torch.empty((self.n_tiles, self.max_h, self.max_w, 4), dtype=torch.uint8,
