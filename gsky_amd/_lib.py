@@ -127,6 +127,8 @@ EXPORTS = [
     "gskyhip_fuse_layers", "gskyhip_fuse_render",
     "gskyhip_inflate_blocks", "gskyhip_inflate_blocks_host", "gskyhip_geotiff_read_decode",
     "gskyhip_netcdf_read_decode", "gskyhip_register_geotiff_decode", "gskyhip_register_netcdf_decode",
+    "gskyhip_deflate_bound", "gskyhip_deflate_workspace_size", "gskyhip_deflate_blocks", "gskyhip_deflate_blocks_host",
+    "gskyhip_encode_netcdf_deflate",
 ]
 
 DECODE_HOST, DECODE_DEVICE = 0, 1
@@ -180,6 +182,16 @@ def lib() -> C.CDLL:
         L.gskyhip_netcdf_read_decode.argtypes = [C.c_char_p, ci, vp, i64, ci, vp, vp]
         L.gskyhip_register_geotiff_decode.argtypes = [C.c_char_p, ci, ci, ci, ci]
         L.gskyhip_register_netcdf_decode.argtypes = [C.c_char_p, ci, ci, ci, ci]
+    if hasattr(L, "gskyhip_deflate_blocks"):   # absent from kept earlier builds (GSKYHIP_LIB=<name>)
+        L.gskyhip_deflate_bound.argtypes = [i64]
+        L.gskyhip_deflate_bound.restype = i64
+        L.gskyhip_deflate_workspace_size.argtypes = [ci, i64]
+        L.gskyhip_deflate_workspace_size.restype = i64
+        L.gskyhip_deflate_blocks.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, i64, vp, vp, vp]
+        L.gskyhip_deflate_blocks_host.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, vp]
+        L.gskyhip_encode_netcdf_deflate.argtypes = [C.POINTER(vp), ci, ci, ci, ci, C.POINTER(d), ci, vp,
+                                                    C.POINTER(C.c_char_p), ci, ci, ci, ci, vp, i64,
+                                                    C.POINTER(i64), vp, vp]
     L.warp_operation_fast.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(d), vp, C.c_char_p, C.POINTER(d),
                                       ci, ci, ci, ci, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci),
                                       C.POINTER(d), C.POINTER(ci), C.POINTER(ci)]

@@ -22,8 +22,10 @@
 // layouts (v3) indexed by a version-1 B-tree.  No HDF5 or netCDF library is
 // in the image: the files are checked by the product's own reader (hdf5.cpp,
 // ingest.hip) and structurally (tests/test_netcdf_out.py) -- parity with
-// GDAL's bytes unpinned.  The compression runs on host threads (zlib), one
-// chunk (row) at a time, after one device-to-host copy of each band.
+// GDAL's bytes unpinned.  The chunk bytes of a band come from one of two
+// providers: host threads (zlib), one chunk (row) at a time, after one
+// device-to-host copy of each band; or the device (deflate.hip: shuffle and
+// Deflate in HBM, slab by slab, only the compressed bytes copied back).
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 
@@ -33,11 +35,13 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../include/gskyhip.h"
+#include "deflate.h"
 
 namespace gsky {
 namespace {
@@ -412,46 +416,84 @@ extern "C" int64_t gskyhip_netcdf_bound(int width, int height, int n_bands, int 
   bool us;
   if (width <= 0 || height <= 0 || n_bands <= 0 || !nc_type_of(dtype, kind, es, us)) return -1;
   const int64_t row = (int64_t)width * es;
+  // also covers the device path's chunks: compressBound(n) = n + n/4096 + n/16384 + n/2^25 + 13 and
+  // gskyhip_deflate_bound(n) = n + 5 * (n / 65535) + 11 (integer divisions); n / 4096 >= 15 * (n / 65535),
+  // so compressBound(n) + 16 >= gskyhip_deflate_bound(n) for every n
   const int64_t zrow = (int64_t)compressBound((uLong)row) + 16;
   const int64_t btree_nodes = (height + 63) / 64 * 2 + 8;
   return (int64_t)n_bands * ((int64_t)height * zrow + btree_nodes * (24 + 64 * 40 + 32 + 8) + 8192) +
          ((int64_t)width + height) * 8 + 65536 + 16384;
 }
 
-// The file from host bands (each height x width of dtype, row-major; NULL or
-// an "EmptyTile" name: a skipped band of zeros).
-static int encode_netcdf_host(const void *const *bands, int n_bands, int dtype, int width, int height,
-                              const double *geot, int epsg, const char *srs, const double *nodata,
-                              const char *const *names, int zlevel, int n_threads, uint8_t *out, int64_t capacity,
-                              int64_t *size) {
+// The chunk bytes of band k: z[j] = the stored bytes of file row j (file row
+// j = image row height - 1 - j; shuffle, then a zlib stream).  Returns a
+// GSKYHIP_* code.
+using ChunkProvider = std::function<int(int k, std::vector<std::vector<uint8_t>> &z)>;
+
+// The host provider: bands are host arrays (each height x width of dtype,
+// row-major; NULL or an "EmptyTile" name: a skipped band of zeros), widened to
+// the file type (UInt16 -> int32) and compressed with zlib on n_threads.
+static ChunkProvider host_chunks(const void *const *bands, int dtype, int width, int height,
+                                 const char *const *names, int zlevel, int n_threads) {
+  return [=](int k, std::vector<std::vector<uint8_t>> &z) -> int {
+    char kind;
+    int es;
+    bool unsigned_att;
+    if (!nc_type_of(dtype, kind, es, unsigned_att)) return GSKYHIP_E_ARG;
+    const int ss = src_size(dtype);
+    const int64_t npx = (int64_t)width * height;
+    std::vector<uint8_t> host((size_t)(npx * es), 0);
+    const bool empty = names && is_empty_tile(names[k]);
+    if (!empty && bands[k]) {   // else EncodeGdal skips the band: its samples stay the dataset fill (0)
+      const uint8_t *raw = (const uint8_t *)bands[k];
+      if (dtype == GSKYHIP_UINT16) {
+        for (int64_t i = 0; i < npx; i++) {
+          uint16_t v;
+          std::memcpy(&v, &raw[(size_t)i * 2], 2);
+          const int32_t w = v;
+          std::memcpy(&host[(size_t)i * 4], &w, 4);
+        }
+      } else {
+        std::memcpy(host.data(), raw, (size_t)(npx * ss));
+      }
+    }
+    const size_t row_bytes = (size_t)width * es;
+    // compress the rows on host threads
+    std::atomic<int> next{0};
+    std::atomic<int> fail{0};
+    auto work = [&]() {
+      std::vector<uint8_t> shuf(row_bytes);
+      for (;;) {
+        const int j = next.fetch_add(1);
+        if (j >= height) break;
+        const uint8_t *src = host.data() + (size_t)(height - 1 - j) * row_bytes;
+        for (int b = 0; b < es; b++)   // shuffle: byte b of every element, then byte b + 1
+          for (int i = 0; i < width; i++) shuf[(size_t)b * width + i] = src[(size_t)i * es + b];
+        uLongf zl = compressBound((uLong)row_bytes);
+        z[j].resize(zl);
+        if (compress2(z[j].data(), &zl, shuf.data(), (uLong)row_bytes, zlevel) != Z_OK) fail = 1;
+        z[j].resize(zl);
+      }
+    };
+    const int nt = std::max(1, std::min(n_threads > 0 ? n_threads : 1, 64));
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; t++) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    return fail ? GSKYHIP_E_HIP : 0;
+  };
+}
+
+// The file around the chunks `chunks_of` provides.
+static int write_netcdf(int n_bands, int dtype, int width, int height, const double *geot, int epsg, const char *srs,
+                        const double *nodata, const char *const *names, int zlevel, const ChunkProvider &chunks_of,
+                        uint8_t *out, int64_t capacity, int64_t *size) {
   char kind;
   int es;
   bool unsigned_att;
-  if (!bands || n_bands <= 0 || width <= 0 || height <= 0 || !geot || !out || !size || zlevel < 0 || zlevel > 9 ||
+  if (n_bands <= 0 || width <= 0 || height <= 0 || !geot || !out || !size || zlevel < 0 || zlevel > 9 ||
       !nc_type_of(dtype, kind, es, unsigned_att))
     return GSKYHIP_E_ARG;
-  const int ss = src_size(dtype);
-  // ---- the bands widened to the file type (UInt16 -> int32)
-  const int64_t npx = (int64_t)width * height;
-  std::vector<std::vector<uint8_t>> host(n_bands);
-  for (int k = 0; k < n_bands; k++) {
-    host[k].assign((size_t)(npx * es), 0);
-    const bool empty = names && is_empty_tile(names[k]);
-    if (empty || !bands[k]) {   // EncodeGdal skips the band: its samples stay the dataset fill (0)
-      continue;
-    }
-    const uint8_t *raw = (const uint8_t *)bands[k];
-    if (dtype == GSKYHIP_UINT16) {
-      for (int64_t i = 0; i < npx; i++) {
-        uint16_t v;
-        std::memcpy(&v, &raw[(size_t)i * 2], 2);
-        const int32_t w = v;
-        std::memcpy(&host[k][(size_t)i * 4], &w, 4);
-      }
-    } else {
-      std::memcpy(host[k].data(), raw, (size_t)(npx * ss));
-    }
-  }
   std::vector<Att> crs_atts;
   bool geographic = false;
   gskyhip_crs crs;
@@ -545,33 +587,11 @@ static int encode_netcdf_host(const void *const *bands, int n_bands, int dtype, 
     links.push_back({"crs", ohdr(img, msgs)});
   }
   // ---- the bands: chunks of one row, shuffle + deflate, bottom-up
-  const size_t row_bytes = (size_t)width * es;
   for (int k = 0; k < n_bands; k++) {
     const bool empty = names && is_empty_tile(names[k]);
-    // compress the rows on host threads (file row j = image row height - 1 - j)
     std::vector<std::vector<uint8_t>> z((size_t)height);
-    std::atomic<int> next{0};
-    std::atomic<int> fail{0};
-    auto work = [&]() {
-      std::vector<uint8_t> shuf(row_bytes);
-      for (;;) {
-        const int j = next.fetch_add(1);
-        if (j >= height) break;
-        const uint8_t *src = host[k].data() + (size_t)(height - 1 - j) * row_bytes;
-        for (int b = 0; b < es; b++)   // shuffle: byte b of every element, then byte b + 1
-          for (int i = 0; i < width; i++) shuf[(size_t)b * width + i] = src[(size_t)i * es + b];
-        uLongf zl = compressBound((uLong)row_bytes);
-        z[j].resize(zl);
-        if (compress2(z[j].data(), &zl, shuf.data(), (uLong)row_bytes, zlevel) != Z_OK) fail = 1;
-        z[j].resize(zl);
-      }
-    };
-    const int nt = std::max(1, std::min(n_threads > 0 ? n_threads : 1, 64));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    if (fail) return GSKYHIP_E_HIP;
+    const int prc = chunks_of(k, z);
+    if (prc) return prc;
     std::vector<ChunkRec> chunks((size_t)height);
     for (int j = 0; j < height; j++) {
       chunks[j].row = (uint64_t)j;
@@ -669,6 +689,15 @@ static int encode_netcdf_host(const void *const *bands, int n_bands, int dtype, 
   return 0;
 }
 
+static int encode_netcdf_host(const void *const *bands, int n_bands, int dtype, int width, int height,
+                              const double *geot, int epsg, const char *srs, const double *nodata,
+                              const char *const *names, int zlevel, int n_threads, uint8_t *out, int64_t capacity,
+                              int64_t *size) {
+  if (!bands) return GSKYHIP_E_ARG;
+  return write_netcdf(n_bands, dtype, width, height, geot, epsg, srs, nodata, names, zlevel,
+                      host_chunks(bands, dtype, width, height, names, zlevel, n_threads), out, capacity, size);
+}
+
 extern "C" int gskyhip_encode_netcdf_host(const void *const *bands, int n_bands, int dtype, int width, int height,
                                           const double *geot, int epsg, const double *nodata,
                                           const char *const *names, int zlevel, int n_threads, uint8_t *out,
@@ -707,4 +736,77 @@ extern "C" int gskyhip_encode_netcdf(const void *const *bands, int n_bands, int 
   if (hipStreamSynchronize(s) != hipSuccess) return GSKYHIP_E_HIP;
   return encode_netcdf_host(ptrs.data(), n_bands, dtype, width, height, geot, epsg, nullptr, nodata, names, zlevel,
                             n_threads, out, capacity, size);
+}
+
+// The device provider: every band's chunks shuffled and deflated in HBM, slab
+// by slab (deflate.hip); a skipped band's all-zero row is compressed once, by
+// the encoder's host twin (the same bytes), and reused for every row.
+static int encode_netcdf_device(const void *const *bands, int n_bands, int dtype, int width, int height,
+                                const double *geot, int epsg, const double *nodata, const char *const *names,
+                                int zlevel, int slab_rows, uint8_t *out, int64_t capacity, int64_t *size,
+                                int64_t *stats, hipStream_t s) {
+  char kind;
+  int es;
+  bool unsigned_att;
+  if (!bands || n_bands <= 0 || width <= 0 || height <= 0 || zlevel < 0 || zlevel > 9 ||
+      !nc_type_of(dtype, kind, es, unsigned_att))
+    return GSKYHIP_E_ARG;
+  const int ss = src_size(dtype);
+  const int64_t row_bytes = (int64_t)width * es;
+  const int rows = nc_slab_rows(row_bytes, height, slab_rows);
+  const int64_t ws_bytes = nc_deflate_workspace(row_bytes, rows);
+  uint8_t *ws = nullptr;
+  if (hipMalloc((void **)&ws, (size_t)ws_bytes) != hipSuccess) return GSKYHIP_E_HIP;
+  int64_t st[4] = {0, 0, 0, ws_bytes};
+  std::vector<uint8_t> zero_chunk;
+  ChunkProvider dev = [&](int k, std::vector<std::vector<uint8_t>> &z) -> int {
+    if (!bands[k] || (names && is_empty_tile(names[k]))) {
+      if (zero_chunk.empty()) {
+        const std::vector<uint8_t> zeros((size_t)row_bytes, 0);
+        const int64_t off = 0, cap = gskyhip_deflate_bound(row_bytes);
+        int32_t status = 0;
+        int64_t len = 0;
+        zero_chunk.resize((size_t)cap);
+        const int rc = gskyhip_deflate_blocks_host(zeros.data(), &off, &row_bytes, 1, zero_chunk.data(), &off, &cap, 1,
+                                                   zlevel, &status, &len);
+        if (rc || status) return GSKYHIP_E_HIP;
+        zero_chunk.resize((size_t)len);
+      }
+      for (auto &row : z) row = zero_chunk;
+      return 0;
+    }
+    for (int j0 = 0; j0 < height; j0 += rows) {
+      const int r = std::min(rows, height - j0);
+      const int rc = nc_deflate_slab(bands[k], ss, es, width, height, j0, r, zlevel, ws, ws_bytes, z, &st[2], s);
+      if (rc) return rc;
+      st[0] += r;
+      st[1] += (int64_t)r * width * ss;
+    }
+    return 0;
+  };
+  const int rc = write_netcdf(n_bands, dtype, width, height, geot, epsg, nullptr, nodata, names, zlevel, dev, out,
+                              capacity, size);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  if (!rc && stats) std::memcpy(stats, st, sizeof(st));
+  return rc;
+}
+
+extern "C" int gskyhip_encode_netcdf_deflate(const void *const *bands, int n_bands, int dtype, int width, int height,
+                                             const double *geot, int epsg, const double *nodata,
+                                             const char *const *names, int zlevel, int n_threads, int deflate,
+                                             int slab_rows, uint8_t *out, int64_t capacity, int64_t *size,
+                                             int64_t *stats, void *stream) {
+  if (deflate == GSKYHIP_DEFLATE_HOST) {
+    if (stats) std::memset(stats, 0, 4 * sizeof(int64_t));
+    return gskyhip_encode_netcdf(bands, n_bands, dtype, width, height, geot, epsg, nodata, names, zlevel, n_threads,
+                                 out, capacity, size, stream);
+  }
+  if (deflate != GSKYHIP_DEFLATE_DEVICE) return GSKYHIP_E_ARG;
+  try {
+    return encode_netcdf_device(bands, n_bands, dtype, width, height, geot, epsg, nodata, names, zlevel, slab_rows, out,
+                                capacity, size, stats, (hipStream_t)stream);
+  } catch (...) {
+    return GSKYHIP_E_HIP;
+  }
 }

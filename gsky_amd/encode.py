@@ -78,13 +78,27 @@ def encode_geotiff(bands: Sequence[torch.Tensor], geot: Sequence[float], epsg: i
     return out[:size.value].tobytes()
 
 
+DEFLATE_HOST, DEFLATE_DEVICE = 0, 1
+
+
 def encode_netcdf(bands: Sequence[torch.Tensor], geot: Sequence[float], epsg: int,
                   nodata: Optional[Sequence[float]] = None, names: Optional[Sequence[str]] = None,
-                  zlevel: int = 6, uint16: bool = False, threads: int = 16) -> bytes:
+                  zlevel: int = 6, uint16: bool = False, threads: int = 16, deflate: str = "host",
+                  slab_rows: int = 0, return_stats: bool = False):
     """netCDF bytes of a coverage: what EncodeGdal writes for format
     "netcdf" with COMPRESS=DEFLATE, ZLEVEL=6 (utils/ogc_encoders.go:263-301):
     `bands` (height, width) device tensors of one dtype (uint8, int8, int16 --
-    uint16 when `uint16`, the bits held in int16 --, float32)."""
+    uint16 when `uint16`, the bits held in int16 --, float32).
+    deflate="host": the rows are compressed by `threads` host threads (zlib)
+    after a copy of each band to the host.  deflate="device": the chunks are
+    shuffled and deflated in HBM, in slabs of `slab_rows` rows (0: the
+    library's choice), and only compressed bytes are copied
+    (gskyhip_encode_netcdf_deflate); the file differs from the host one in
+    the chunk payloads only.  return_stats: also the tuple (chunks deflated
+    on the device, raw bytes read from HBM, compressed bytes copied to the
+    host, device workspace bytes)."""
+    if deflate not in ("host", "device"):
+        raise ValueError('deflate must be "host" or "device", not %r' % (deflate,))
     if not bands:
         raise ValueError("encode_netcdf: no bands")
     dt = bands[0].dtype
@@ -104,11 +118,84 @@ def encode_netcdf(bands: Sequence[torch.Tensor], geot: Sequence[float], epsg: in
     gt = (C.c_double * 6)(*[float(v) for v in geot])
     nd = np.asarray(nodata, np.float64) if nodata is not None else None
     nm = (C.c_char_p * n)(*[s.encode() for s in names]) if names is not None else None
-    check(L.gskyhip_encode_netcdf(ptrs, n, code, w, h, gt, int(epsg),
-                                  nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm, int(zlevel),
-                                  int(threads), out.ctypes.data_as(C.c_void_p), cap, C.byref(size),
-                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)), "encode_netcdf")
-    return out[:size.value].tobytes()
+    if deflate == "host" and not return_stats:
+        check(L.gskyhip_encode_netcdf(ptrs, n, code, w, h, gt, int(epsg),
+                                      nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm, int(zlevel),
+                                      int(threads), out.ctypes.data_as(C.c_void_p), cap, C.byref(size),
+                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)), "encode_netcdf")
+        return out[:size.value].tobytes()
+    stats = (C.c_int64 * 4)()
+    with torch.cuda.device(bands[0].device):
+        check(L.gskyhip_encode_netcdf_deflate(ptrs, n, code, w, h, gt, int(epsg),
+                                              nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm,
+                                              int(zlevel), int(threads),
+                                              DEFLATE_DEVICE if deflate == "device" else DEFLATE_HOST, int(slab_rows),
+                                              out.ctypes.data_as(C.c_void_p), cap, C.byref(size), stats,
+                                              C.c_void_p(torch.cuda.current_stream(bands[0].device).cuda_stream)),
+              "encode_netcdf_deflate")
+    data = out[:size.value].tobytes()
+    return (data, tuple(stats)) if return_stats else data
+
+
+def deflate_bound(n: int) -> int:
+    """gskyhip_deflate_bound: the most bytes deflate_blocks gives for n input bytes."""
+    return int(lib().gskyhip_deflate_bound(int(n)))
+
+
+def deflate_blocks(blocks, zlib_wrapper: bool = True, level: int = 6, where: str = "device", out_caps=None,
+                   return_status: bool = False, fill: int = 0xA5):
+    """Compress every block (a bytes-like object) on its own into a zlib
+    (zlib_wrapper) or raw Deflate stream: gskyhip_deflate_blocks on the
+    current device and stream (where="device") or its host twin
+    (where="host"), the counterpart of ingest.inflate_blocks.  Returns the
+    list of streams.  out_caps[k] (default: gskyhip_deflate_bound) is block
+    k's output capacity; return_status: instead the tuple (status list,
+    out_len list, the output ranges as uint8 arrays of the full capacities,
+    pre-filled with `fill`), so that a caller can see what was not written."""
+    if where not in ("device", "host"):
+        raise ValueError('where must be "device" or "host"')
+    blocks = [bytes(b) for b in blocks]
+    n = len(blocks)
+    L = lib()
+    in_len = np.array([len(b) for b in blocks], np.int64).reshape(n)
+    in_off = np.zeros(n, np.int64)
+    if n:
+        in_off[1:] = np.cumsum(in_len)[:-1]
+    src = np.frombuffer(b"".join(blocks) + b"\0", np.uint8).copy()   # never empty
+    out_cap = np.array([L.gskyhip_deflate_bound(int(v)) for v in in_len] if out_caps is None else list(out_caps),
+                       np.int64).reshape(n)
+    out_off = np.zeros(n, np.int64)
+    if n:
+        out_off[1:] = np.cumsum(out_cap)[:-1]
+    total = max(1, int(out_cap.sum()))
+    status = np.full(n, -99, np.int32)
+    out_len = np.full(n, -99, np.int64)
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    if where == "host":
+        dst = np.full(total, fill, np.uint8)
+        rc = L.gskyhip_deflate_blocks_host(p(src), p(in_off), p(in_len), n, p(dst), p(out_off), p(out_cap),
+                                           int(bool(zlib_wrapper)), int(level), p(status), p(out_len))
+    else:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        dsrc = torch.from_numpy(src).to(dev)
+        ddst = torch.full((total,), fill, dtype=torch.uint8, device=dev)
+        ws_bytes = max(16, int(L.gskyhip_deflate_workspace_size(n, int(in_len.sum()))))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        rc = L.gskyhip_deflate_blocks(C.c_void_p(dsrc.data_ptr()), p(in_off), p(in_len), n,
+                                      C.c_void_p(ddst.data_ptr()), p(out_off), p(out_cap), int(bool(zlib_wrapper)),
+                                      int(level), C.c_void_p(ws.data_ptr()), ws_bytes, p(status), p(out_len),
+                                      C.c_void_p(stream.cuda_stream))
+        with torch.cuda.stream(stream):
+            dst = ddst.cpu().numpy()
+    check(rc, "deflate_blocks")
+    if return_status:
+        return ([int(x) for x in status], [int(x) for x in out_len],
+                [dst[int(out_off[k]):int(out_off[k] + out_cap[k])] for k in range(n)])
+    for k in range(n):
+        if status[k] != 0:
+            raise ValueError("deflate_blocks: block %d has status %d" % (k, int(status[k])))
+    return [dst[int(out_off[k]):int(out_off[k] + out_len[k])].tobytes() for k in range(n)]
 
 
 def encode_netcdf_host(bands: Sequence[np.ndarray], geot: Sequence[float], epsg: int,

@@ -319,6 +319,33 @@ int gskyhip_inflate_blocks(const uint8_t *dev_in, const int64_t *in_off, const i
 int gskyhip_inflate_blocks_host(const uint8_t *in, const int64_t *in_off, const int64_t *in_len, int n_blocks,
                                 uint8_t *out, const int64_t *out_off, const int64_t *out_cap,
                                 const int64_t *out_need, int zlib_wrapper, int32_t *status, int64_t *out_len);
+/* ---- Deflate encoded on the GPU: the mirror of gskyhip_inflate_blocks ------ */
+/* n_blocks independent blocks: block k, dev_in[in_off[k] .. + in_len[k]), is
+ * compressed on its own into a complete RFC 1950 stream (zlib_wrapper 1:
+ * header 78 9C, Adler-32) or a raw RFC 1951 stream (zlib_wrapper 0) at
+ * dev_out[out_off[k] .. ).  level 0: stored blocks only; levels 1-9: the one
+ * device encoding (csrc/deflate_core.h) -- of a dynamic-Huffman block, a
+ * fixed-Huffman block and stored blocks the one whose stream is the shortest,
+ * so out_len[k] <= gskyhip_deflate_bound(in_len[k]) for every input.  The
+ * stream length is known before a byte is written: when it exceeds out_cap[k]
+ * the block gets GSKYHIP_INFLATE_E_CAP, none of its bytes is written and
+ * out_len[k] is the length it needs.  The offset / length arrays and status /
+ * out_len (n_blocks each) are HOST memory; in_len[k] <= 2^30.  No byte outside
+ * a block's ranges is read or written.  The bytes depend only on the block's
+ * bytes, zlib_wrapper and level.  workspace: device memory of at least
+ * gskyhip_deflate_workspace_size(n_blocks, sum of in_len) bytes (about 5.3
+ * times the input).  Returns GSKYHIP_OK once the launch has completed (the
+ * call waits for `stream`).  The _host twin gives the same bytes from the same
+ * encoder on up to 16 host threads over host pointers, without a workspace. */
+int64_t gskyhip_deflate_bound(int64_t in_len);   /* in_len + 5 * (in_len / 65535 + 1) + 6 */
+int64_t gskyhip_deflate_workspace_size(int n_blocks, int64_t total_in_len);
+int gskyhip_deflate_blocks(const uint8_t *dev_in, const int64_t *in_off, const int64_t *in_len, int n_blocks,
+                           uint8_t *dev_out, const int64_t *out_off, const int64_t *out_cap, int zlib_wrapper,
+                           int level, void *workspace, int64_t workspace_bytes, int32_t *status, int64_t *out_len,
+                           void *stream);
+int gskyhip_deflate_blocks_host(const uint8_t *in, const int64_t *in_off, const int64_t *in_len, int n_blocks,
+                                uint8_t *out, const int64_t *out_off, const int64_t *out_cap, int zlib_wrapper,
+                                int level, int32_t *status, int64_t *out_len);
 /* gskyhip_geotiff_read / gskyhip_netcdf_read with the block decode on the
  * device.  decode = GSKYHIP_DECODE_HOST is exactly the call without _decode.
  * GSKYHIP_DECODE_DEVICE: the band's *compressed* blocks go to HBM in one copy,
@@ -831,6 +858,32 @@ int64_t gskyhip_netcdf_bound(int width, int height, int n_bands, int dtype);
 int gskyhip_encode_netcdf(const void *const *bands, int n_bands, int dtype, int width, int height,
                           const double *geot, int epsg, const double *nodata, const char *const *names, int zlevel,
                           int n_threads, uint8_t *out, int64_t capacity, int64_t *size, void *stream);
+/* gskyhip_encode_netcdf with a choice of where the chunks are compressed.
+ * deflate = GSKYHIP_DEFLATE_HOST is exactly gskyhip_encode_netcdf.
+ * GSKYHIP_DEFLATE_DEVICE: a kernel reads the band in HBM and writes the file's
+ * chunks in file order (file row j = image row height - 1 - j; UInt16 widened
+ * to int32; the HDF5 shuffle applied), gskyhip_deflate_blocks' kernels turn
+ * each chunk into a zlib stream, the streams are packed on the device and come
+ * back with their lengths -- two small copies (lengths, statuses) and one copy
+ * of exactly the compressed bytes per slab.  The host allocates them into the
+ * image and writes the B-tree and headers.  Everything but the chunk payloads
+ * (and what follows from their sizes: addresses, B-tree keys) is what the host
+ * path writes for the same arguments; the filter message records zlevel (0:
+ * stored blocks; 1-9: the one device encoding).  Work proceeds in slabs of
+ * slab_rows rows; <= 0: the library's choice, 16 MiB of raw chunk bytes (at
+ * least one row, at most 65536 rows), which caps the device workspace --
+ * allocated once per call and freed before return -- at about 8.4 times that,
+ * 135 MiB, whatever the height (rows above 16 MiB: 8.4 times one row).  The
+ * file does not depend on slab_rows.  n_threads is used by the host mode only.
+ * stats (HOST int64[4], or NULL) = {chunks deflated on the device, raw bytes
+ * read from HBM, compressed bytes copied to the host, device workspace bytes};
+ * all zero in the host mode. */
+#define GSKYHIP_DEFLATE_HOST 0
+#define GSKYHIP_DEFLATE_DEVICE 1
+int gskyhip_encode_netcdf_deflate(const void *const *bands, int n_bands, int dtype, int width, int height,
+                                  const double *geot, int epsg, const double *nodata, const char *const *names,
+                                  int zlevel, int n_threads, int deflate, int slab_rows, uint8_t *out,
+                                  int64_t capacity, int64_t *size, int64_t *stats, void *stream);
 /* The same from HOST bands (EncodeGdal's rasters are host memory in the
  * reference): no device involved. */
 int gskyhip_encode_netcdf_host(const void *const *bands, int n_bands, int dtype, int width, int height,
