@@ -128,7 +128,7 @@ EXPORTS = [
     "gskyhip_inflate_blocks", "gskyhip_inflate_blocks_host", "gskyhip_geotiff_read_decode",
     "gskyhip_netcdf_read_decode", "gskyhip_register_geotiff_decode", "gskyhip_register_netcdf_decode",
     "gskyhip_deflate_bound", "gskyhip_deflate_workspace_size", "gskyhip_deflate_blocks", "gskyhip_deflate_blocks_host",
-    "gskyhip_encode_netcdf_deflate",
+    "gskyhip_encode_netcdf_deflate", "gskyhip_png_deflate_rows_host",
 ]
 
 DECODE_HOST, DECODE_DEVICE = 0, 1
@@ -192,6 +192,8 @@ def lib() -> C.CDLL:
         L.gskyhip_encode_netcdf_deflate.argtypes = [C.POINTER(vp), ci, ci, ci, ci, C.POINTER(d), ci, vp,
                                                     C.POINTER(C.c_char_p), ci, ci, ci, ci, vp, i64,
                                                     C.POINTER(i64), vp, vp]
+    if hasattr(L, "gskyhip_png_deflate_rows_host"):   # absent from kept earlier builds (GSKYHIP_LIB=<name>)
+        L.gskyhip_png_deflate_rows_host.argtypes = [vp, ci, ci, ci, ci, vp, i64, vp]
     L.warp_operation_fast.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(d), vp, C.c_char_p, C.POINTER(d),
                                       ci, ci, ci, ci, C.POINTER(vp), C.POINTER(ci), C.POINTER(ci),
                                       C.POINTER(d), C.POINTER(ci), C.POINTER(ci)]

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(64) void deflate_write_kernel(const uint8_t *__rest
   for (int64_t i = lane; i < nw; i += 64) words[i] = 0;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
   __syncthreads();
-  if (lane == 0) gd::write_frame(P, zlib_wrapper, adler, words);
+  if (lane == 0) gd::write_frame(P, zlib_wrapper, gd::kFlgDefault, adler, words);
   const int64_t nseg = (n + gd::kSeg - 1) / gd::kSeg;
   int64_t running = (zlib_wrapper ? 16 : 0) + P.hdr_bits;
   for (int64_t s0 = 0; s0 < nseg; s0 += 64) {

@@ -1,10 +1,13 @@
-// deflate_core.h -- the Deflate encoder of independent blocks (RFC 1950 /
-// 1951), compiled for the host and for the device: the
-// tokeniser of one segment, the length-limited Huffman construction, the
-// block plan (dynamic / fixed / stored, the smallest), the header writer and
-// the bit sink.  deflate.hip runs these functions with a lane per segment and
-// a wave per block; the host twin runs the same functions in a loop, so both
-// give the same bytes.
+// deflate_core.h -- the one Deflate encoder (RFC 1950 / 1951), compiled for
+// the host and for the device: two tokenisers (a segment of an
+// independent block; a row of a PNG image), the length-limited Huffman
+// construction, the block plan in parts (build_dynamic, finish_plan) with each
+// user's choice of block type on top (plan_block: the smallest of dynamic /
+// fixed / stored; plan_png: fixed or dynamic), the header writer and the bit
+// sink.  deflate.hip runs these functions with a lane per segment and a wave
+// per block, encode.hip with a thread per image row and a workgroup per tile;
+// the host twins (encode_block_host, encode_rows_host) run the same functions
+// in a loop, so each gives its device's bytes.
 //
 // A block of n bytes is cut into segments of kSeg bytes.  A segment's tokens
 // depend only on the block's bytes: a match starts and ends inside its
@@ -42,6 +45,8 @@ constexpr int kLitN = 286, kDistN = 30, kClN = 19, kSymN = kLitN + kDistN;
 constexpr int kHdrWords = 160;   // room of a dynamic block header (at most 4.5 kbit)
 constexpr uint32_t kAdlerMod = 65521u;
 constexpr int kStoredMax = 65535;
+// FLG of the zlib header after CMF 0x78, (0x78 * 256 + FLG) % 31 == 0: default level / fastest
+constexpr uint32_t kFlgDefault = 0x9C, kFlgFastest = 0x01;
 
 enum Mode { kDynamic = 0, kFixed = 1, kStored = 2 };
 enum Status { kOk = 0, kOutputFull = 5 };   // GSKYHIP_INFLATE_OK, GSKYHIP_INFLATE_E_CAP
@@ -96,6 +101,19 @@ GSKY_DF_HD uint32_t tok_pack(int sym, uint32_t lx, int dc, uint32_t dx) {
   return (uint32_t)sym | ((uint32_t)(dc + 1) << 9) | (lx << 14) | (dx << 19);
 }
 
+// the token of a literal byte / of a match of length l at distance d; add(sym)
+// counts a literal / length symbol, add(kLitN + dc) a distance symbol
+template <class Add> GSKY_DF_HD uint32_t literal_token(uint8_t byte, Add &&add) {
+  add((int)byte);
+  return tok_pack((int)byte, 0u, -1, 0u);
+}
+template <class Add> GSKY_DF_HD uint32_t match_token(int l, int d, Add &&add) {
+  const int lc = len_code(l), dc = dist_code(d);
+  add(257 + lc);
+  add(kLitN + dc);
+  return tok_pack(257 + lc, (uint32_t)(l - len_base(lc)), dc, (uint32_t)(d - dist_base(dc)));
+}
+
 // length of the match of data[p ..) with data[p - d ..), at most lim
 GSKY_DF_HD int match_len(const uint8_t *data, int64_t p, int d, int lim) {
   int l = 0;
@@ -141,16 +159,70 @@ GSKY_DF_HD int tokenize_segment(const uint8_t *data, int64_t p0, int64_t p1, uin
       }
     }
     if (best >= 3) {
-      const int lc = len_code(best), dc = dist_code(bd);
-      tok[n++] = tok_pack(257 + lc, (uint32_t)(best - len_base(lc)), dc, (uint32_t)(bd - dist_base(dc)));
-      add(257 + lc);
-      add(kLitN + dc);
+      tok[n++] = match_token(best, bd, add);
       if (best <= 16)   // short matches keep the table fresh; long runs need no entries
         for (int64_t r = p + 1; r < p + best && r + 3 <= p1; r++) hash[hash3(data + r) * hstride] = (uint16_t)(r - p0 + 1);
       p += best;
     } else {
-      tok[n++] = tok_pack((int)data[p], 0u, -1, 0u);
-      add((int)data[p]);
+      tok[n++] = literal_token(data[p], add);
+      p++;
+    }
+  }
+  return n;
+}
+
+// The PNG encoder's matcher, over rows of `stride` filtered bytes (bpp bytes a
+// pixel): the candidates at p are the distances a PNG of upsampled tiles
+// repeats at -- runs (1), the pixel to the left and 2-3 pixels back, the
+// pixels above (1-3 rows) and the diagonals --, the one saving the most bits
+// by a static estimate wins (6.5 bits per literal byte against ~7 bits of
+// length code plus the distance code and its extra bits).  A match ends
+// before p1 and reaches back to data[0] at most, never past the window.
+GSKY_DF_HD void row_best_match(const uint8_t *data, int64_t p, int64_t p1, int bpp, int stride, int &best, int &bd) {
+  best = 0;
+  bd = 0;
+  int bscore = -(1 << 30);
+  const int dists[11] = {1, bpp, stride, 2 * bpp, 3 * bpp, 2 * stride, stride - bpp, stride + bpp,
+                         2 * stride - bpp, 2 * stride + bpp, 3 * stride};
+  const int lim = (int)(p1 - p < 258 ? p1 - p : 258);
+#pragma unroll
+  for (int c = 0; c < 11; c++) {
+    const int d = dists[c];
+    if (d < 1 || p - d < 0 || d > 32768) continue;   // (d < 1: only rows shorter than a pixel)
+    const int l = match_len(data, p, d, lim);
+    if (l < 3) continue;
+    const int score = 13 * l - 2 * (7 + 5 + dist_extra(dist_code(d)));   // 2x the bits saved
+    if (score > bscore) { bscore = score; best = l; bd = d; }
+  }
+}
+
+// The tokens of row [p0, p1) of an image data[0 ..): tok[0 .. return), at
+// most p1 - p0 of them; add() as in tokenize_segment.  One step of lazy
+// matching: a match starting one byte later that is 2+ bytes longer wins, the
+// byte going out as a literal.
+template <class Add>
+GSKY_DF_HD int tokenize_row(const uint8_t *data, int64_t p0, int64_t p1, int bpp, int stride, uint32_t *tok,
+                            Add &&add) {
+  int n = 0;
+  int64_t p = p0;
+  while (p < p1) {
+    int best, bd;
+    row_best_match(data, p, p1, bpp, stride, best, bd);
+    if (best >= 3 && p + 1 < p1) {
+      int b2, d2;
+      row_best_match(data, p + 1, p1, bpp, stride, b2, d2);
+      if (b2 > best + 1) {
+        tok[n++] = literal_token(data[p], add);
+        p++;
+        best = b2;
+        bd = d2;
+      }
+    }
+    if (best >= 3) {
+      tok[n++] = match_token(best, bd, add);
+      p += best;
+    } else {
+      tok[n++] = literal_token(data[p], add);
       p++;
     }
   }
@@ -163,6 +235,7 @@ struct HuffScratch {
   int16_t sorted[kLitN];
   int16_t parent[2 * kLitN];
   uint8_t depth[2 * kLitN];
+  int32_t bl_count[16], next[16];   // codes per length, next code of a length (not on a lane's stack)
 };
 
 // Code lengths <= maxbits for n symbols (n <= kLitN): a Huffman tree by the
@@ -184,20 +257,24 @@ GSKY_DF_HD int huff_lengths(const uint32_t *freq, int n, int maxbits, uint8_t *l
       m++;
     }
   auto wf = [&](int s) -> uint32_t { return freq[s] ? freq[s] : ((s == forced0 || s == forced1) ? 1u : 0u); };
-  // insertion sort by (weight, symbol): symbols arrive in ascending order
+  // the leaves sorted by (weight, symbol): a Shell sort (gaps 121, 40, 13, 4,
+  // 1), since one thread sorts up to 286 leaves; no two keys are equal, so the
+  // order is the only one
   int k = 0;
-  for (int s = 0; s < n; s++) {
-    const uint32_t w = wf(s);
-    if (!w) continue;
-    int i = k++;
-    while (i > 0 && H.weight[i - 1] > w) {
-      H.weight[i] = H.weight[i - 1];
-      H.sorted[i] = H.sorted[i - 1];
-      i--;
+  for (int s = 0; s < n; s++)
+    if (wf(s)) { H.weight[k] = wf(s); H.sorted[k++] = (int16_t)s; }
+  for (int gap = 121; gap > 0; gap /= 3)
+    for (int j = gap; j < m; j++) {
+      const uint32_t w = H.weight[j];
+      const int16_t s = H.sorted[j];
+      int i = j;
+      for (; i >= gap && (H.weight[i - gap] > w || (H.weight[i - gap] == w && H.sorted[i - gap] > s)); i -= gap) {
+        H.weight[i] = H.weight[i - gap];
+        H.sorted[i] = H.sorted[i - gap];
+      }
+      H.weight[i] = w;
+      H.sorted[i] = s;
     }
-    H.weight[i] = w;
-    H.sorted[i] = (int16_t)s;
-  }
   int il = 0, in = m, nx = m;
   for (int j = 0; j < m - 1; j++) {
     int a, b;
@@ -209,7 +286,9 @@ GSKY_DF_HD int huff_lengths(const uint32_t *freq, int n, int maxbits, uint8_t *l
     nx++;
   }
   const int root = nx - 1;
-  int bl_count[16];
+  int32_t *bl_count = H.bl_count;
+  // (the loops over code lengths stay rolled: unrolled, they hold the counters in ~40 registers a lane)
+#pragma nounroll
   for (int b = 0; b < 16; b++) bl_count[b] = 0;
   int overflow = 0;
   H.depth[root] = 0;
@@ -232,6 +311,7 @@ GSKY_DF_HD int huff_lengths(const uint32_t *freq, int n, int maxbits, uint8_t *l
     overflow -= 2;
   }
   int i = 0;
+#pragma nounroll
   for (int bits = maxbits; bits >= 1; bits--)
     for (int c = bl_count[bits]; c > 0 && i < m; c--) len[H.sorted[i++]] = (uint8_t)bits;
   uint64_t kraft = 0;
@@ -241,13 +321,15 @@ GSKY_DF_HD int huff_lengths(const uint32_t *freq, int n, int maxbits, uint8_t *l
 }
 
 // canonical codes (3.2.2), bit-reversed for LSB-first output
-GSKY_DF_HD void huff_codes(const uint8_t *len, int n, uint16_t *code) {
-  int bl[16], next[16];
+GSKY_DF_HD void huff_codes(const uint8_t *len, int n, uint16_t *code, HuffScratch &H) {
+  int32_t *bl = H.bl_count, *next = H.next;
+#pragma nounroll
   for (int b = 0; b < 16; b++) bl[b] = 0;
   for (int s = 0; s < n; s++) bl[len[s]]++;
   bl[0] = 0;
   int c = 0;
   next[0] = 0;
+#pragma nounroll
   for (int b = 1; b < 16; b++) { c = (c + bl[b - 1]) << 1; next[b] = c; }
   for (int s = 0; s < n; s++) code[s] = len[s] ? (uint16_t)rev_bits((uint32_t)next[len[s]]++, len[s]) : 0;
 }
@@ -282,19 +364,20 @@ GSKY_DF_HD int cl_order(int k) {
   return o[k];
 }
 
-// The plan of a block of n bytes whose tokens have the histogram freq
-// (freq[256] is set to 1 here: the end of block).  level 0: stored blocks.
-GSKY_DF_HD void plan_block(uint32_t *freq, int64_t n, int zlib_wrapper, int level, Plan &P, PlanScratch &S) {
-  const int64_t wrap = zlib_wrapper ? 6 : 0;
-  P.limited = 0;
-  P.hdr_bits = 0;
-  P.body_bits = 0;
-  const int64_t stored = stored_bytes(n);
-  if (level == 0) {
-    P.mode = kStored;
-    P.stream_bytes = stored + wrap;
-    return;
-  }
+// What the dynamic code of a histogram costs, beside the fixed code: bits of
+// the tokens with the end of block (the extra bits in both), bits of the
+// dynamic header, and what finish_plan needs to write that header.
+struct DynCode {
+  int64_t dyn_bits, fix_bits, hdr_bits;
+  int32_t ok;        // the lengths are complete prefix codes and the header fits Plan::hdr
+  int32_t limited;   // the length limiter ran
+  int32_t hlit, hdist, hclen, nr;
+};
+
+// The dynamic code of the histogram freq (freq[256] is set to 1 here: the end
+// of block): its lengths into P.len, the code-length code and the run-length
+// coded lengths into S.
+GSKY_DF_HD DynCode build_dynamic(uint32_t *freq, Plan &P, PlanScratch &S) {
   freq[256] = 1;
   int64_t extra = 0;
   for (int lc = 0; lc < 29; lc++) extra += (int64_t)freq[257 + lc] * len_extra(lc);
@@ -346,16 +429,15 @@ GSKY_DF_HD void plan_block(uint32_t *freq, int64_t n, int zlib_wrapper, int leve
     dyn += (int64_t)freq[kLitN + d] * P.len[kLitN + d];
     fix += (int64_t)freq[kLitN + d] * 5;
   }
-  // the three candidates in bytes (the bodies include the end of block)
-  const int64_t dyn_bytes = (ok && hb <= (int64_t)kHdrWords * 32) ? (hb + dyn + 7) / 8 : INT64_MAX;
-  const int64_t fix_bytes = (3 + fix + 7) / 8;
-  if (stored <= dyn_bytes && stored <= fix_bytes) {
-    P.mode = kStored;
-    P.stream_bytes = stored + wrap;
-    return;
-  }
-  if (fix_bytes <= dyn_bytes) {
-    P.mode = kFixed;
+  return {dyn, fix, hb, ok && hb <= (int64_t)kHdrWords * 32, limited, hlit, hdist, hclen, nr};
+}
+
+// The plan of a block in `mode` (kDynamic after build_dynamic, which D comes
+// from, or kFixed): the codes and the block header.  The body's bits and the
+// stream's length are the caller's to set (set_body).
+GSKY_DF_HD void finish_plan(Plan &P, PlanScratch &S, const DynCode &D, int mode) {
+  P.mode = mode;
+  if (mode == kFixed) {
     for (int v = 0; v < kLitN; v++) {
       uint32_t c;
       int l;
@@ -366,15 +448,13 @@ GSKY_DF_HD void plan_block(uint32_t *freq, int64_t n, int zlib_wrapper, int leve
     for (int d = 0; d < kDistN; d++) { P.code[kLitN + d] = (uint16_t)rev_bits((uint32_t)d, 5); P.len[kLitN + d] = 5; }
     P.hdr[0] = 0x3u;   // BFINAL 1, BTYPE 01
     P.hdr_bits = 3;
-    P.body_bits = fix - 7;
-    P.stream_bytes = fix_bytes + wrap;
+    P.limited = 0;
     return;
   }
-  P.mode = kDynamic;
-  P.limited = limited;
-  huff_codes(P.len, kLitN, P.code);
-  huff_codes(P.len + kLitN, kDistN, P.code + kLitN);
-  huff_codes(S.cll, kClN, S.clc);
+  P.limited = D.limited;
+  huff_codes(P.len, kLitN, P.code, S.H);
+  huff_codes(P.len + kLitN, kDistN, P.code + kLitN, S.H);
+  huff_codes(S.cll, kClN, S.clc, S.H);
   uint64_t acc = 0;
   int nacc = 0, word = 0;
   auto put = [&](uint32_t bits, int nb) {
@@ -383,11 +463,11 @@ GSKY_DF_HD void plan_block(uint32_t *freq, int64_t n, int zlib_wrapper, int leve
     if (nacc >= 32) { P.hdr[word++] = (uint32_t)acc; acc >>= 32; nacc -= 32; }
   };
   put(0x5u, 3);   // BFINAL 1, BTYPE 10
-  put((uint32_t)(hlit - 257), 5);
-  put((uint32_t)(hdist - 1), 5);
-  put((uint32_t)(hclen - 4), 4);
-  for (int k = 0; k < hclen; k++) put(S.cll[cl_order(k)], 3);
-  for (int k = 0; k < nr; k++) {
+  put((uint32_t)(D.hlit - 257), 5);
+  put((uint32_t)(D.hdist - 1), 5);
+  put((uint32_t)(D.hclen - 4), 4);
+  for (int k = 0; k < D.hclen; k++) put(S.cll[cl_order(k)], 3);
+  for (int k = 0; k < D.nr; k++) {
     const int sym = S.rs[k];
     put(S.clc[sym], S.cll[sym]);
     if (sym == 16) put(S.rx[k], 2);
@@ -395,9 +475,48 @@ GSKY_DF_HD void plan_block(uint32_t *freq, int64_t n, int zlib_wrapper, int leve
     else if (sym == 18) put(S.rx[k], 7);
   }
   if (nacc > 0) P.hdr[word] = (uint32_t)acc;
-  P.hdr_bits = (int32_t)hb;
-  P.body_bits = dyn - P.len[256];
-  P.stream_bytes = dyn_bytes + wrap;
+  P.hdr_bits = (int32_t)D.hdr_bits;
+}
+
+// body_bits: the tokens' bits under the plan's code; wrap: bytes around the block (zlib: 6)
+GSKY_DF_HD void set_body(Plan &P, int64_t body_bits, int64_t wrap) {
+  P.body_bits = body_bits;
+  P.stream_bytes = wrap + (P.hdr_bits + body_bits + P.len[256] + 7) / 8;
+}
+
+// The plan of an independent block of n bytes whose tokens have the histogram
+// freq: the shortest stream in bytes of stored, fixed and dynamic, ties in
+// that order.  level 0: stored blocks.
+GSKY_DF_HD void plan_block(uint32_t *freq, int64_t n, int zlib_wrapper, int level, Plan &P, PlanScratch &S) {
+  const int64_t wrap = zlib_wrapper ? 6 : 0;
+  DynCode D = {};
+  if (level != 0) D = build_dynamic(freq, P, S);
+  // the three candidates in bytes (the bodies include the end of block)
+  const int64_t stored = stored_bytes(n);
+  const int64_t dyn_bytes = D.ok ? (D.hdr_bits + D.dyn_bits + 7) / 8 : INT64_MAX;
+  const int64_t fix_bytes = level != 0 ? (3 + D.fix_bits + 7) / 8 : INT64_MAX;
+  if (stored <= dyn_bytes && stored <= fix_bytes) {
+    P.mode = kStored;
+    P.limited = 0;
+    P.hdr_bits = 0;
+    P.body_bits = 0;
+    P.stream_bytes = stored + wrap;
+  } else if (fix_bytes <= dyn_bytes) {
+    finish_plan(P, S, D, kFixed);
+    set_body(P, D.fix_bits - 7, wrap);
+  } else {
+    finish_plan(P, S, D, kDynamic);
+    set_body(P, D.dyn_bits - P.len[256], wrap);
+  }
+}
+
+// The PNG encoder's plan of a tile: never stored; the fixed code iff it is
+// asked for, the dynamic code is unusable, or the fixed block is not longer
+// in bits, header included.  The body's bits come with the rows (set_body).
+GSKY_DF_HD void plan_png(uint32_t *freq, int fixed_only, Plan &P, PlanScratch &S) {
+  DynCode D = {};
+  if (!fixed_only) D = build_dynamic(freq, P, S);
+  finish_plan(P, S, D, !D.ok || 3 + D.fix_bits <= D.hdr_bits + D.dyn_bits ? kFixed : kDynamic);
 }
 
 // ---------------------------------------------------------------- the bit sink
@@ -473,12 +592,13 @@ GSKY_DF_HD void or_byte(uint32_t *words, int64_t pos, uint32_t v) {
 }
 
 // What one writer adds around the segments of a Huffman-coded stream: the
-// zlib header, the block header, the end of block and the Adler-32.
-GSKY_DF_HD void write_frame(const Plan &P, int zlib_wrapper, uint32_t adler, uint32_t *words) {
+// zlib header (CMF 0x78: deflate, 32 KiB window; then flg, a kFlg* value),
+// the block header, the end of block and the Adler-32.
+GSKY_DF_HD void write_frame(const Plan &P, int zlib_wrapper, uint32_t flg, uint32_t adler, uint32_t *words) {
   const int64_t base = zlib_wrapper ? 16 : 0;
   if (zlib_wrapper) {
-    or_byte(words, 0, 0x78);   // CMF: deflate, 32 KiB window
-    or_byte(words, 1, 0x9C);   // FLG: default level, (0x78 * 256 + 0x9C) % 31 == 0
+    or_byte(words, 0, 0x78);
+    or_byte(words, 1, flg);
   }
   BitSink bs;
   bs.init(words, base);
@@ -503,7 +623,7 @@ GSKY_DF_HD void write_frame(const Plan &P, int zlib_wrapper, uint32_t adler, uin
 GSKY_DF_HD uint8_t stored_byte(int64_t j, const uint8_t *data, int64_t n, int zlib_wrapper, uint32_t adler) {
   if (zlib_wrapper) {
     if (j == 0) return 0x78;
-    if (j == 1) return 0x9C;
+    if (j == 1) return kFlgDefault;
     j -= 2;
   }
   const int64_t body = stored_bytes(n);
@@ -574,7 +694,7 @@ inline void encode_block_host(const uint8_t *src, int64_t n, uint8_t *dst, int64
     return;
   }
   std::vector<uint32_t> words((size_t)((total + 3) / 4), 0u);   // exactly the stream: a write past it is out of bounds
-  write_frame(P, zlib_wrapper, adler, words.data());
+  write_frame(P, zlib_wrapper, kFlgDefault, adler, words.data());
   int64_t at = (zlib_wrapper ? 16 : 0) + P.hdr_bits;
   for (int64_t seg = 0; seg < nseg; seg++) {
     const uint32_t *tk = tok.data() + seg * kSeg;
@@ -582,6 +702,41 @@ inline void encode_block_host(const uint8_t *src, int64_t n, uint8_t *dst, int64
     at += segment_bits(tk, ntok[(size_t)seg], P.len);
   }
   memcpy(dst, words.data(), (size_t)total);
+}
+
+// The PNG encoder's zlib stream of h rows of `stride` filtered bytes on the
+// host: the functions the PNG kernels run, row after row.  Status and *out_len
+// as in encode_block_host.
+inline int32_t encode_rows_host(const uint8_t *rows, int h, int stride, int bpp, int fixed_only, uint8_t *dst,
+                                int64_t cap, int64_t *out_len) {
+  const int64_t n = (int64_t)h * stride;
+  std::vector<uint32_t> tok((size_t)n), freq(kSymN, 0u);
+  std::vector<int32_t> ntok((size_t)h);
+  for (int y = 0; y < h; y++) {
+    const int64_t p0 = (int64_t)y * stride;
+    ntok[(size_t)y] = tokenize_row(rows, p0, p0 + stride, bpp, stride, tok.data() + p0, [&](int sym) {
+      if (!fixed_only) freq[(size_t)sym]++;
+    });
+  }
+  std::vector<Plan> Pv(1);
+  std::vector<PlanScratch> Sv(1);
+  Plan &P = Pv[0];
+  plan_png(freq.data(), fixed_only, P, Sv[0]);
+  int64_t body = 0;
+  for (int y = 0; y < h; y++) body += segment_bits(tok.data() + (int64_t)y * stride, ntok[(size_t)y], P.len);
+  set_body(P, body, 6);
+  *out_len = P.stream_bytes;
+  if (P.stream_bytes > cap) return kOutputFull;
+  std::vector<uint32_t> words((size_t)((P.stream_bytes + 3) / 4), 0u);   // exactly the stream, as above
+  write_frame(P, 1, kFlgFastest, adler32_serial(rows, n), words.data());
+  int64_t at = 16 + P.hdr_bits;
+  for (int y = 0; y < h; y++) {
+    const uint32_t *tk = tok.data() + (int64_t)y * stride;
+    write_segment(tk, ntok[(size_t)y], P.code, P.len, words.data(), at);
+    at += segment_bits(tk, ntok[(size_t)y], P.len);
+  }
+  memcpy(dst, words.data(), (size_t)P.stream_bytes);
+  return kOk;
 }
 
 }  // namespace deflate

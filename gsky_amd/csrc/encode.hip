@@ -16,11 +16,16 @@
 //     through a 32 KiB bufio.Writer: IDAT chunks of exactly 32768 bytes, the
 //     last one shorter; IHDR / IDAT / IEND with their CRC-32.
 // Here the colour-type test, the NRGBA conversion and the filter selection run
-// on the GPU (one workgroup per row), the deflate of each tile on host threads
-// (zlib 1.2.11, level 6, 32 KiB window, default strategy).  The filtered rows
-// -- every byte zlib receives -- are Go's exactly; the compressed bytes are
-// zlib's, not Go's compress/flate (both DEFLATE: the decoded image and the
-// filter bytes are identical, byte identity with Go is parity unpinned).
+// on the GPU (one workgroup per row), and so does the deflate of each tile
+// ("GPU deflate" below: the encoder of deflate_core.h, one final Huffman-coded
+// block per tile) and the CRC-32 of its IDAT chunks; host threads only frame
+// the PNGs.  Tiles of more than 4096 rows, and every tile under
+// GSKYHIP_PNG_ZLIB=1, are deflated by zlib (level 6, 32 KiB window, default
+// strategy) on host threads instead.  The filtered rows -- every byte the
+// deflate receives -- are Go's exactly; the compressed bytes are this
+// encoder's (or zlib's), not Go's compress/flate (all DEFLATE: the decoded
+// image and the filter bytes are identical, byte identity with Go is parity
+// unpinned).
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 
@@ -34,6 +39,7 @@
 #include <vector>
 
 #include "../../include/gskyhip.h"
+#include "deflate_core.h"
 
 namespace gsky {
 namespace {
@@ -151,276 +157,31 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const uint8_t *__restri
 // The zlib stream of each tile's filtered rows built on the GPU: one final
 // block -- Huffman codes built for the tile from its symbol frequencies
 // (RFC 1951 3.2.7), or the fixed codes (3.2.6) where those come out shorter
-// -- whose LZ77 matches are
-// searched at the distances a PNG row offers -- runs, pixels to the left,
-// rows above and the diagonals (deflate_tokens) -- within the row (so rows
-// are encoded independently: a workgroup per tile, a thread per row, matches
-// may reach back into earlier rows).  Pass 1 counts each row's bits; their prefix sums place every row
-// in the tile's bit stream and every tile in one packed buffer (so only the
-// compressed bytes cross PCIe); pass 2 writes the codes (the words two rows
-// share by OR).  Adler-32 from per-row sums.  The stream is valid DEFLATE /
-// zlib; its bytes are neither zlib's nor Go's compress/flate (parity
-// unpinned; the tests inflate it and compare the rows).
-__constant__ uint16_t kLenBase[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59,
-                                      67, 83, 99, 115, 131, 163, 195, 227, 258};
-__constant__ uint8_t kLenExtra[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
-__constant__ uint16_t kDistBase[30] = {1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769,
-                                       1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577};
-__constant__ uint8_t kDistExtra[30] = {0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10,
-                                       11, 11, 12, 12, 13, 13};
+// -- whose LZ77 matches are searched at the distances a PNG row offers --
+// runs, pixels to the left, rows above and the diagonals (tokenize_row) --
+// within the row (so rows are encoded independently: a thread per row, matches
+// may reach back into earlier rows).  Pass 1 counts each row's bits; their
+// prefix sums place every row in the tile's bit stream and every tile in one
+// packed buffer (so only the compressed bytes cross PCIe); pass 2 writes the
+// codes (the words two rows share by OR).  Adler-32 from per-row sums.  The
+// stream is valid DEFLATE / zlib; its bytes are neither zlib's nor Go's
+// compress/flate (parity unpinned; the tests inflate it, compare the rows, and
+// hold the bytes to tests/golden/png_streams.json).
+//
+// The encoder is deflate_core.h, shared with the block encoder
+// of deflate.hip and with the host twin gskyhip_png_deflate_rows_host: its row
+// tokeniser, Huffman construction, block plan (plan_png: fixed or dynamic,
+// never stored), bit sink and frame writer.  PNG's own are the geometry below,
+// the per-row Adler-32 and the 4-byte aligned packing of the streams.
+namespace gd = deflate;
 
 constexpr int kPngMaxRows = 4096;    // rows of a tile the deflate kernels handle (LDS scan)
 
-struct BitSink {   // LSB-first bit writer over 32-bit words; first and last words by OR
-  uint32_t *out;
-  uint64_t acc;
-  int nacc;
-  int64_t word;
-  bool first;
-  __device__ void init(uint32_t *o, int64_t bitpos) {
-    out = o; word = bitpos >> 5; nacc = (int)(bitpos & 31); acc = 0; first = true;
-  }
-  __device__ __forceinline__ void put(uint32_t bits, int n) {
-    acc |= (uint64_t)bits << nacc;
-    nacc += n;
-    if (nacc >= 32) {
-      if (first) { atomicOr(out + word, (uint32_t)acc); first = false; }
-      else out[word] = (uint32_t)acc;
-      acc >>= 32;
-      nacc -= 32;
-      word++;
-    }
-  }
-  __device__ void finish() {
-    if (nacc > 0) atomicOr(out + word, (uint32_t)acc);
-  }
-};
-
-__device__ __forceinline__ uint32_t rev_bits(uint32_t code, int len) { return __brev(code) >> (32 - len); }
-
-typedef uint32_t u32_unaligned __attribute__((aligned(1)));
-__device__ __forceinline__ uint32_t ld_u32(const uint8_t *p) { return *(const u32_unaligned *)p; }
-
-// fixed Huffman code of a literal / length symbol, bit-reversed for LSB-first output
-__device__ __forceinline__ void lit_code(int v, uint32_t &code, int &len) {
-  if (v < 144) { code = 0x30 + v; len = 8; }
-  else if (v < 256) { code = 0x190 + (v - 144); len = 9; }
-  else if (v < 280) { code = v - 256; len = 7; }
-  else { code = 0xC0 + (v - 280); len = 8; }
-  code = rev_bits(code, len);
-}
-
-// One row's LZ77 tokens, in order, to f(sym, len_extra, n_len_extra, dcode,
-// dist_extra, n_dist_extra): dcode < 0 for a literal.  Candidates at the
-// distances a PNG of upsampled tiles repeats at -- runs (1), the pixel to the
-// left and 2-3 pixels back, the pixels above (1-3 rows) and the diagonals --
-// the one saving the most bits by a static estimate (6.5 bits per literal
-// byte against ~7 bits of length code plus the distance code and its extra
-// bits), and one step of lazy matching (a match starting one byte later that
-// is 2+ bytes longer wins, the byte going out as a literal).  A model of
-// these tokens with dynamic Huffman costs: 461 -> 433 KB per C2 tile (zlib
-// level 6: 409 KB).
-__device__ __forceinline__ int dist_code(int d) {
-  int dc = 0;
-  while (dc < 29 && kDistBase[dc + 1] <= d) dc++;
-  return dc;
-}
-
-__device__ __forceinline__ void best_match(const uint8_t *__restrict__ data, int64_t p, int64_t p1, int bpp,
-                                           int stride, int &best, int &bd) {
-  best = 0;
-  bd = 0;
-  int bscore = -(1 << 30);
-  const int dists[11] = {1, bpp, stride, 2 * bpp, 3 * bpp, 2 * stride, stride - bpp, stride + bpp,
-                         2 * stride - bpp, 2 * stride + bpp, 3 * stride};
-  const int lim = (int)min((int64_t)258, p1 - p);
-#pragma unroll
-  for (int c = 0; c < 11; c++) {
-    const int d = dists[c];
-    if (p - d < 0 || d > 32768) continue;
-    int l = 0;
-    // 4 bytes per compare (unaligned dword loads), the first difference by ctz
-    while (l + 4 <= lim) {
-      const uint32_t x = ld_u32(data + p + l) ^ ld_u32(data + p + l - d);
-      if (x) { l += __builtin_ctz(x) >> 3; goto done; }
-      l += 4;
-    }
-    while (l < lim && data[p + l] == data[p + l - d]) l++;
-  done:
-    if (l < 3) continue;
-    const int score = 13 * l - 2 * (7 + 5 + (int)kDistExtra[dist_code(d)]);   // 2x the bits saved
-    if (score > bscore) { bscore = score; best = l; bd = d; }
-  }
-}
-
-template <class F>
-__device__ __forceinline__ void deflate_tokens(const uint8_t *__restrict__ data, int64_t p0, int64_t p1, int bpp,
-                                               int stride, F &&f) {
-  int64_t p = p0;
-  while (p < p1) {
-    int best, bd;
-    best_match(data, p, p1, bpp, stride, best, bd);
-    if (best >= 3 && p + 1 < p1) {   // lazy: a longer match one byte on
-      int b2, d2;
-      best_match(data, p + 1, p1, bpp, stride, b2, d2);
-      if (b2 > best + 1) {
-        f((int)data[p], 0u, 0, -1, 0u, 0);
-        p++;
-        best = b2;
-        bd = d2;
-      }
-    }
-    if (best >= 3) {
-      int lc = 0;
-      while (lc < 28 && kLenBase[lc + 1] <= best) lc++;
-      const int dc = dist_code(bd);
-      f(257 + lc, (uint32_t)(best - kLenBase[lc]), (int)kLenExtra[lc], dc, (uint32_t)(bd - kDistBase[dc]),
-        (int)kDistExtra[dc]);
-      p += best;
-    } else {
-      f((int)data[p], 0u, 0, -1, 0u, 0);
-      p++;
-    }
-  }
-}
-
-// The tokens of a row are searched once (pass 1) and kept, packed one per
-// dword -- symbol (9 bits) | distance code + 1 (5) | length extra (5) |
-// distance extra (13) -- for the bit count and the write pass to replay.
-__device__ __forceinline__ uint32_t tok_pack(int sym, uint32_t lx, int dc, uint32_t dx) {
-  return (uint32_t)sym | ((uint32_t)(dc + 1) << 9) | (lx << 14) | (dx << 19);
-}
-
-template <class F>
-__device__ __forceinline__ void tok_replay(const uint32_t *__restrict__ tk, int n, F &&f) {
-  for (int i = 0; i < n; i++) {
-    const uint32_t v = tk[i];
-    const int sym = (int)(v & 511u), dc = (int)((v >> 9) & 31u) - 1;
-    f(sym, (v >> 14) & 31u, sym >= 257 ? (int)kLenExtra[sym - 257] : 0, dc, v >> 19, dc >= 0 ? (int)kDistExtra[dc] : 0);
-  }
-}
-
-// ---- per-tile Huffman codes (round 4: one dynamic block per tile, RFC 1951
-// 3.2.7, or the fixed codes where those are shorter)
-constexpr int kLitN = 286, kDistN = 30, kClN = 19, kSymN = kLitN + kDistN;
-__constant__ uint8_t kClOrder[kClN] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-struct PngTab {   // a tile's codes (global, written by pass 1, read by pass 2)
-  uint32_t hdr[160];        // the block header, LSB-first: BFINAL, BTYPE and (dynamic) the code lengths
-  uint16_t code[kSymN];     // literal / length codes then distance codes, bit-reversed
-  uint8_t len[kSymN];
-  int32_t hdr_bits;
-};
-
-struct HuffLds {   // scratch of one code construction (thread 0 but the rank sort)
-  uint32_t wf[kLitN];       // frequencies, at least two of them non-zero
-  int16_t sorted[kLitN];    // symbols by ascending (frequency, symbol)
-  uint32_t weight[2 * kLitN];
-  int16_t parent[2 * kLitN];
-  uint8_t depth[2 * kLitN];
-  int32_t m, ok;
-};
-
-// Code lengths <= maxbits of the n symbols with frequencies `freq` (a
-// Huffman tree by the two-queue merge over the sorted leaves; lengths past
-// maxbits folded back as zlib's gen_bitlen does; least frequent symbols take
-// the longest codes).  All threads call it; H.ok = 0 if the result is not a
-// complete prefix code (the caller then uses the fixed codes).
-__device__ void huff_lengths(const uint32_t *freq, int n, int maxbits, uint8_t *len, HuffLds &H) {
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    int m = 0;
-    for (int s = 0; s < n; s++) { H.wf[s] = freq[s]; m += freq[s] ? 1 : 0; }
-    for (int s = 0; m < 2 && s < n; s++)   // a code needs two leaves (zlib forces them too)
-      if (!H.wf[s]) { H.wf[s] = 1; m++; }
-    H.m = m;
-  }
-  __syncthreads();
-  for (int s = tid; s < n; s += blockDim.x) {   // rank of (freq, symbol) among the used symbols
-    len[s] = 0;
-    if (!H.wf[s]) continue;
-    const uint64_t key = ((uint64_t)H.wf[s] << 9) | (uint64_t)s;
-    int r = 0;
-    for (int q = 0; q < n; q++)
-      if (H.wf[q] && (((uint64_t)H.wf[q] << 9) | (uint64_t)q) < key) r++;
-    H.sorted[r] = (int16_t)s;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const int m = H.m;
-    for (int i = 0; i < m; i++) H.weight[i] = H.wf[H.sorted[i]];
-    int il = 0, in = m, nx = m;   // leaf queue, internal queue (ascending by construction)
-    auto take = [&]() {
-      if (il < m && (in >= nx || H.weight[il] <= H.weight[in])) return il++;
-      return in++;
-    };
-    for (int k = 0; k < m - 1; k++) {
-      const int a = take(), b = take();
-      H.weight[nx] = H.weight[a] + H.weight[b];
-      H.parent[a] = (int16_t)nx; H.parent[b] = (int16_t)nx;
-      nx++;
-    }
-    const int root = nx - 1;
-    int bl_count[16] = {0};
-    int overflow = 0;
-    H.depth[root] = 0;
-    for (int i = root - 1; i >= 0; i--) {
-      const int d = H.depth[H.parent[i]] + 1;
-      H.depth[i] = (uint8_t)min(d, 255);
-      // every node past maxbits counts, internal ones too (as in zlib, where a
-      // clamped parent clamps its children): k leaves under a node at maxbits
-      // come with k - 2 internal nodes and need (2k - 2) / 2 = k - 1 moves
-      if (d > maxbits) overflow++;
-      if (i < m) bl_count[min(d, maxbits)]++;
-    }
-    while (overflow > 0) {   // zlib gen_bitlen: move leaves until the code fits
-      int bits = maxbits - 1;
-      while (bits > 0 && bl_count[bits] == 0) bits--;
-      if (bits == 0) break;
-      bl_count[bits]--;
-      bl_count[bits + 1] += 2;
-      bl_count[maxbits]--;
-      overflow -= 2;
-    }
-    // longest codes to the least frequent symbols
-    int i = 0;
-    for (int bits = maxbits; bits >= 1; bits--)
-      for (int c = bl_count[bits]; c > 0 && i < m; c--) len[H.sorted[i++]] = (uint8_t)bits;
-    uint64_t kraft = 0;   // complete: sum 2^(maxbits - len) == 2^maxbits
-    for (int s = 0; s < n; s++)
-      if (len[s]) kraft += 1ull << (maxbits - len[s]);
-    H.ok = (i == m && kraft == (1ull << maxbits)) ? 1 : 0;
-  }
-  __syncthreads();
-}
-
-// canonical codes (RFC 1951 3.2.2), bit-reversed for LSB-first output
-__device__ void huff_codes(const uint8_t *len, int n, uint16_t *code) {
-  int bl[16] = {0}, next[16];
-  for (int s = 0; s < n; s++) bl[len[s]]++;
-  bl[0] = 0;
-  int c = 0;
-  for (int b = 1; b < 16; b++) { c = (c + bl[b - 1]) << 1; next[b] = c; }
-  for (int s = 0; s < n; s++)
-    code[s] = len[s] ? (uint16_t)rev_bits((uint32_t)next[len[s]]++, len[s]) : 0;
-}
-
-__device__ void fixed_table(PngTab &T) {
-  for (int v = 0; v < kLitN; v++) {
-    uint32_t c;
-    int l;
-    lit_code(v, c, l);
-    T.code[v] = (uint16_t)c; T.len[v] = (uint8_t)l;
-  }
-  for (int d = 0; d < kDistN; d++) { T.code[kLitN + d] = (uint16_t)rev_bits((uint32_t)d, 5); T.len[kLitN + d] = 5; }
-  T.hdr[0] = 0x3u;   // BFINAL 1, BTYPE 01
-  T.hdr_bits = 3;
-}
-
 // Pass 0, a thread per row (a wave per 64 rows of a tile, so every CU holds
-// many rows in flight): the row's tokens, kept for pass 1's bit count and
-// pass 2, and -- for a dynamic code -- their symbol frequencies, summed per
-// workgroup in LDS and added to the tile's global histogram.
+// many rows in flight): the row's tokens, one dword each, kept for pass 1's
+// bit count and pass 2 (a row has at most `stride` tokens), and -- for a
+// dynamic code -- their symbol frequencies, summed per workgroup in LDS and
+// added to the tile's global histogram.
 __global__ __launch_bounds__(64) void png_tokenize_kernel(const uint8_t *__restrict__ filt,
                                                           const int64_t *__restrict__ off,
                                                           const int32_t *__restrict__ wh,
@@ -432,41 +193,36 @@ __global__ __launch_bounds__(64) void png_tokenize_kernel(const uint8_t *__restr
   const int h = wh[2 * t + 1];
   const int bpp = opaque[t] ? 3 : 4;
   const int stride = 1 + bpp * wh[2 * t];
-  const uint8_t *data = filt + off[t];
-  __shared__ uint32_t s_freq[kSymN];
-  for (int i = tid; i < kSymN; i += 64) s_freq[i] = 0;
+  __shared__ uint32_t s_freq[gd::kSymN];
+  for (int i = tid; i < gd::kSymN; i += 64) s_freq[i] = 0;
   __syncthreads();
   if (y < h) {
     const int64_t p0 = (int64_t)y * stride;
-    uint32_t *tk = tok + (int64_t)t * per + p0;   // a row has at most `stride` tokens
-    int n = 0;
-    deflate_tokens(data, p0, p0 + stride, bpp, stride, [&](int sym, uint32_t lx, int, int dc, uint32_t dx, int) {
-      tk[n++] = tok_pack(sym, lx, dc, dx);
-      if (dynamic) {
-        atomicAdd(&s_freq[sym], 1u);
-        if (dc >= 0) atomicAdd(&s_freq[kLitN + dc], 1u);
-      }
-    });
-    ntok[(int64_t)t * max_h + y] = n;
+    ntok[(int64_t)t * max_h + y] =
+        gd::tokenize_row(filt + off[t], p0, p0 + stride, bpp, stride, tok + (int64_t)t * per + p0, [&](int sym) {
+          if (dynamic) atomicAdd(&s_freq[sym], 1u);
+        });
   }
   __syncthreads();
   if (dynamic)
-    for (int i = tid; i < kSymN; i += 64)
-      if (s_freq[i]) atomicAdd(&freq[(int64_t)t * kSymN + i], s_freq[i]);
+    for (int i = tid; i < gd::kSymN; i += 64)
+      if (s_freq[i]) atomicAdd(&freq[(int64_t)t * gd::kSymN + i], s_freq[i]);
 }
 
-// Pass 1, a workgroup per tile: the rows' Adler-32 sums; the tile's dynamic
-// code from pass 0's frequencies (or the fixed one where that is shorter,
-// header included) into tab[t]; each row's bits under it; the stream length.
-// Tile stream: zlib header (2 B), block header, rows, end of block, pad to a
-// byte, Adler-32 (4 B).
+static_assert(sizeof(gd::Plan) % 4 == 0, "a tile's plan is copied in dwords");
+
+// Pass 1, a workgroup per tile: the rows' Adler-32 sums; the tile's plan from
+// pass 0's frequencies (thread 0: the dynamic code, or the fixed one where
+// that is not longer, header included); each row's bits under it; the stream
+// length; the plan into tab[t] for pass 2.  Tile stream: zlib header (2 B),
+// block header, rows, end of block, pad to a byte, Adler-32 (4 B).
 __global__ __launch_bounds__(256) void png_deflate_count_kernel(const uint8_t *__restrict__ filt,
                                                                 const int64_t *__restrict__ off,
                                                                 const int32_t *__restrict__ wh,
                                                                 const int32_t *__restrict__ opaque, int max_h,
                                                                 int32_t *__restrict__ row_bits,
                                                                 uint32_t *__restrict__ adler,
-                                                                int64_t *__restrict__ zlen, PngTab *__restrict__ tab,
+                                                                int64_t *__restrict__ zlen, gd::Plan *__restrict__ tab,
                                                                 int dynamic, const uint32_t *__restrict__ tok,
                                                                 const int32_t *__restrict__ ntok, int64_t per,
                                                                 const uint32_t *__restrict__ freq) {
@@ -477,22 +233,16 @@ __global__ __launch_bounds__(256) void png_deflate_count_kernel(const uint8_t *_
   const uint8_t *data = filt + off[t];
   __shared__ uint32_t s_a[kPngMaxRows], s_b[kPngMaxRows];
   __shared__ int64_t s_bits[256];
-  __shared__ uint32_t s_freq[kSymN], s_clf[kClN];
-  __shared__ uint8_t s_len[kSymN], s_cll[kClN];
-  __shared__ uint16_t s_code[kSymN], s_clc[kClN];
-  __shared__ uint8_t s_rs[kSymN];     // code-length RLE: symbols
-  __shared__ uint8_t s_rx[kSymN];     // and their extra values
-  __shared__ int32_t s_nr, s_hlit, s_hdist, s_use_fixed;
-  __shared__ HuffLds H;
-  PngTab &T = tab[t];
-  for (int i = tid; i < kSymN; i += blockDim.x) s_freq[i] = dynamic ? freq[(int64_t)t * kSymN + i] : 0u;
-  __syncthreads();
+  __shared__ uint32_t s_freq[gd::kSymN];
+  __shared__ gd::Plan P;
+  __shared__ gd::PlanScratch S;
+  for (int i = tid; i < gd::kSymN; i += blockDim.x) s_freq[i] = dynamic ? freq[(int64_t)t * gd::kSymN + i] : 0u;
   for (int y = tid; y < h; y += blockDim.x) {
     const int64_t p0 = (int64_t)y * stride;
     uint64_t a = 0, bb = 0;   // sum of bytes, sum of (n - i) * byte (exact: < 2^40), then mod 65521
     int i = 0;
     for (; i + 4 <= stride; i += 4) {
-      const uint32_t v = ld_u32(data + p0 + i);
+      const uint32_t v = gd::ld_u32(data + p0 + i);
       const uint32_t c0 = v & 0xFFu, c1 = (v >> 8) & 0xFFu, c2 = (v >> 16) & 0xFFu, c3 = v >> 24;
       a += c0 + c1 + c2 + c3;
       bb += (uint64_t)(stride - i) * c0 + (uint64_t)(stride - i - 1) * c1 + (uint64_t)(stride - i - 2) * c2 +
@@ -502,114 +252,15 @@ __global__ __launch_bounds__(256) void png_deflate_count_kernel(const uint8_t *_
       a += data[p0 + i];
       bb += (uint64_t)(stride - i) * data[p0 + i];
     }
-    s_a[y] = (uint32_t)(a % 65521u);
-    s_b[y] = (uint32_t)(bb % 65521u);
+    s_a[y] = (uint32_t)(a % gd::kAdlerMod);
+    s_b[y] = (uint32_t)(bb % gd::kAdlerMod);
   }
-  if (tid == 0) { s_freq[256] = 1; s_use_fixed = dynamic ? 0 : 1; }   // end of block
   __syncthreads();
-  if (dynamic) {
-    huff_lengths(s_freq, kLitN, 15, s_len, H);
-    int ok = H.ok;
-    huff_lengths(s_freq + kLitN, kDistN, 15, s_len + kLitN, H);
-    ok &= H.ok;
-    if (tid == 0) {   // HLIT / HDIST, then the run-length coded lengths (16 / 17 / 18)
-      int hlit = kLitN, hdist = kDistN;
-      while (hlit > 257 && !s_len[hlit - 1]) hlit--;
-      while (hdist > 1 && !s_len[kLitN + hdist - 1]) hdist--;
-      s_hlit = hlit; s_hdist = hdist;
-      for (int k = 0; k < kClN; k++) s_clf[k] = 0;
-      const int N = hlit + hdist;
-      auto L = [&](int i) { return i < hlit ? s_len[i] : s_len[kLitN + i - hlit]; };
-      int nr = 0;
-      auto emit = [&](int sym, int x) { s_rs[nr] = (uint8_t)sym; s_rx[nr] = (uint8_t)x; nr++; s_clf[sym]++; };
-      for (int i = 0; i < N;) {
-        const int v = L(i);
-        int run = 1;
-        while (i + run < N && L(i + run) == v) run++;
-        int r = run;
-        if (v == 0) {
-          while (r >= 11) { const int k = min(r, 138); emit(18, k - 11); r -= k; }
-          if (r >= 3) { emit(17, r - 3); r = 0; }
-          while (r > 0) { emit(0, 0); r--; }
-        } else {
-          emit(v, 0); r--;
-          while (r >= 3) { const int k = min(r, 6); emit(16, k - 3); r -= k; }
-          while (r > 0) { emit(v, 0); r--; }
-        }
-        i += run;
-      }
-      s_nr = nr;
-    }
-    __syncthreads();
-    huff_lengths(s_clf, kClN, 7, s_cll, H);
-    ok &= H.ok;
-    if (tid == 0) {
-      huff_codes(s_len, kLitN, s_code);
-      huff_codes(s_len + kLitN, kDistN, s_code + kLitN);
-      huff_codes(s_cll, kClN, s_clc);
-      int hclen = kClN;
-      while (hclen > 4 && !s_cll[kClOrder[hclen - 1]]) hclen--;
-      int64_t hb = 3 + 5 + 5 + 4 + 3 * hclen;
-      for (int k = 0; k < s_nr; k++) {
-        const int sym = s_rs[k];
-        hb += s_cll[sym] + (sym == 16 ? 2 : sym == 17 ? 3 : sym == 18 ? 7 : 0);
-      }
-      // compare with the fixed codes (extra bits are the same under both)
-      int64_t dyn = hb, fix = 3;
-      for (int v = 0; v < kLitN; v++) {
-        uint32_t c;
-        int l;
-        lit_code(v, c, l);
-        dyn += (int64_t)s_freq[v] * s_len[v];
-        fix += (int64_t)s_freq[v] * l;
-      }
-      for (int d = 0; d < kDistN; d++) {
-        dyn += (int64_t)s_freq[kLitN + d] * s_len[kLitN + d];
-        fix += (int64_t)s_freq[kLitN + d] * 5;
-      }
-      if (!ok || hb > 160 * 32 || fix <= dyn) {
-        s_use_fixed = 1;
-      } else {   // the header bits into tab[t].hdr
-        uint64_t acc = 0;
-        int nacc = 0, word = 0;
-        auto put = [&](uint32_t bits, int nb) {
-          acc |= (uint64_t)bits << nacc;
-          nacc += nb;
-          if (nacc >= 32) { T.hdr[word++] = (uint32_t)acc; acc >>= 32; nacc -= 32; }
-        };
-        put(0x5u, 3);   // BFINAL 1, BTYPE 10
-        put((uint32_t)(s_hlit - 257), 5);
-        put((uint32_t)(s_hdist - 1), 5);
-        put((uint32_t)(hclen - 4), 4);
-        for (int k = 0; k < hclen; k++) put(s_cll[kClOrder[k]], 3);
-        for (int k = 0; k < s_nr; k++) {
-          const int sym = s_rs[k];
-          put(s_clc[sym], s_cll[sym]);
-          if (sym == 16) put(s_rx[k], 2);
-          else if (sym == 17) put(s_rx[k], 3);
-          else if (sym == 18) put(s_rx[k], 7);
-        }
-        if (nacc > 0) T.hdr[word] = (uint32_t)acc;
-        T.hdr_bits = (int32_t)hb;
-      }
-    }
-    __syncthreads();
-  }
-  if (s_use_fixed) {
-    if (tid == 0) fixed_table(T);
-    __syncthreads();
-    for (int i = tid; i < kSymN; i += blockDim.x) { s_len[i] = T.len[i]; s_code[i] = T.code[i]; }
-  } else {
-    for (int i = tid; i < kSymN; i += blockDim.x) { T.len[i] = s_len[i]; T.code[i] = s_code[i]; }
-  }
+  if (tid == 0) gd::plan_png(s_freq, !dynamic, P, S);
   __syncthreads();
   int64_t mine = 0;
   for (int y = tid; y < h; y += blockDim.x) {
-    uint32_t b = 0;
-    tok_replay(tok + (int64_t)t * per + (int64_t)y * stride, ntok[(int64_t)t * max_h + y],
-               [&](int sym, uint32_t, int le, int dc, uint32_t, int de) {
-                 b += s_len[sym] + le + (dc >= 0 ? s_len[kLitN + dc] + de : 0);
-               });
+    const uint32_t b = gd::segment_bits(tok + (int64_t)t * per + (int64_t)y * stride, ntok[(int64_t)t * max_h + y], P.len);
     row_bits[(int64_t)t * max_h + y] = (int32_t)b;
     mine += b;
   }
@@ -620,82 +271,49 @@ __global__ __launch_bounds__(256) void png_deflate_count_kernel(const uint8_t *_
     for (int k = 0; k < (int)blockDim.x; k++) total += s_bits[k];
     uint32_t A = 1, B = 0;   // adler32 of the rows in order
     for (int y = 0; y < h; y++) {
-      B = (uint32_t)((B + (uint64_t)stride * A + s_b[y]) % 65521u);
-      A = (A + s_a[y]) % 65521u;
+      B = (uint32_t)((B + (uint64_t)stride * A + s_b[y]) % gd::kAdlerMod);
+      A = (A + s_a[y]) % gd::kAdlerMod;
     }
     adler[t] = (B << 16) | A;
-    const int hdr_bits = s_use_fixed ? 3 : T.hdr_bits;
-    zlen[t] = 2 + (hdr_bits + total + s_len[256] + 7) / 8 + 4;
+    gd::set_body(P, total, 6);
+    zlen[t] = P.stream_bytes;
   }
+  __syncthreads();
+  for (int i = tid; i < (int)(sizeof(gd::Plan) / 4); i += blockDim.x)
+    ((uint32_t *)&tab[t])[i] = ((const uint32_t *)&P)[i];
 }
 
-// Pass 2: the codes of every row at its bit offset in the tile's stream, at
-// the tile's byte offset zoff[t] of the packed buffer (zeroed).
-__global__ __launch_bounds__(256) void png_deflate_write_kernel(const uint8_t *__restrict__ filt,
-                                                                const int64_t *__restrict__ off,
-                                                                const int32_t *__restrict__ wh,
+// Pass 2: the frame (thread 0) and the codes of every row at its bit offset
+// in the tile's stream, at the tile's byte offset zoff[t] of the packed buffer
+// (zeroed; 4-byte aligned, so the stream is the sink's words).
+__global__ __launch_bounds__(256) void png_deflate_write_kernel(const int32_t *__restrict__ wh,
                                                                 const int32_t *__restrict__ opaque, int max_h,
                                                                 const int32_t *__restrict__ row_bits,
                                                                 const uint32_t *__restrict__ adler,
                                                                 const int64_t *__restrict__ zoff,
-                                                                const int64_t *__restrict__ zlen,
                                                                 uint8_t *__restrict__ packed,
-                                                                const PngTab *__restrict__ tab,
+                                                                const gd::Plan *__restrict__ tab,
                                                                 const uint32_t *__restrict__ tok,
                                                                 const int32_t *__restrict__ ntok, int64_t per) {
   const int t = blockIdx.x;
   const int w = wh[2 * t], h = wh[2 * t + 1];
-  const int bpp = opaque[t] ? 3 : 4;
-  const int stride = 1 + bpp * w;
-  (void)filt;
-  uint8_t *z = packed + zoff[t];
-  // the tile's stream starts on a 4-byte boundary of the packed buffer
-  uint32_t *words = (uint32_t *)z;
-  __shared__ int64_t s_start[kPngMaxRows + 1];
-  __shared__ uint16_t s_code[kSymN];
-  __shared__ uint8_t s_len[kSymN];
-  const PngTab &T = tab[t];
-  for (int i = threadIdx.x; i < kSymN; i += blockDim.x) { s_code[i] = T.code[i]; s_len[i] = T.len[i]; }
-  const int hdr_bits = T.hdr_bits;
+  const int stride = 1 + (opaque[t] ? 3 : 4) * w;
+  uint32_t *words = (uint32_t *)(packed + zoff[t]);
+  __shared__ int64_t s_start[kPngMaxRows];
+  __shared__ uint16_t s_code[gd::kSymN];
+  __shared__ uint8_t s_len[gd::kSymN];
+  const gd::Plan &T = tab[t];
+  for (int i = threadIdx.x; i < gd::kSymN; i += blockDim.x) { s_code[i] = T.code[i]; s_len[i] = T.len[i]; }
   if (threadIdx.x == 0) {   // row bit offsets (serial: h <= 4096 adds)
-    int64_t b = 16 + hdr_bits;
+    int64_t b = 16 + T.hdr_bits;
     for (int y = 0; y < h; y++) { s_start[y] = b; b += row_bits[(int64_t)t * max_h + y]; }
-    s_start[h] = b;
   }
   __syncthreads();
-  // every byte by OR into the zeroed buffer, so no write order matters
-  auto or_byte = [&](int64_t pos, uint32_t v) { atomicOr(words + (pos >> 2), (v & 0xFFu) << (8 * (pos & 3))); };
-  if (threadIdx.x == 0) {
-    or_byte(0, 0x78);   // CMF: deflate, 32 KiB window
-    or_byte(1, 0x01);   // FLG: (0x78 * 256 + 0x01) % 31 == 0
-    BitSink bs;         // block header
-    bs.init(words, 16);
-    int k = 0;
-    for (; k + 32 <= hdr_bits; k += 32) bs.put(T.hdr[k >> 5], 32);
-    if (k < hdr_bits) bs.put(T.hdr[k >> 5] & ((1u << (hdr_bits - k)) - 1u), hdr_bits - k);
-    bs.finish();
-    bs.init(words, s_start[h]);   // end of block
-    bs.put(s_code[256], s_len[256]);
-    bs.finish();
-    const int64_t end = (s_start[h] + s_len[256] + 7) / 8;   // Adler-32 after the byte padding
-    const uint32_t ad = adler[t];
-    or_byte(end, ad >> 24); or_byte(end + 1, ad >> 16); or_byte(end + 2, ad >> 8); or_byte(end + 3, ad);
-  }
-  for (int y = threadIdx.x; y < h; y += blockDim.x) {
-    BitSink bs;
-    bs.init(words, s_start[y]);
-    tok_replay(tok + (int64_t)t * per + (int64_t)y * stride, ntok[(int64_t)t * max_h + y],
-               [&](int sym, uint32_t lx, int le, int dc, uint32_t dx, int de) {
-                     bs.put(s_code[sym], s_len[sym]);
-                     if (dc >= 0) {
-                       if (le) bs.put(lx, le);
-                       bs.put(s_code[kLitN + dc], s_len[kLitN + dc]);
-                       if (de) bs.put(dx, de);
-                     }
-                   });
-    bs.finish();
-  }
-  (void)zlen;
+  // every shared word by OR into the zeroed buffer, so no write order matters
+  if (threadIdx.x == 0) gd::write_frame(T, 1, gd::kFlgFastest, adler[t], words);
+  for (int y = threadIdx.x; y < h; y += blockDim.x)
+    gd::write_segment(tok + (int64_t)t * per + (int64_t)y * stride, ntok[(int64_t)t * max_h + y], s_code, s_len, words,
+                      s_start[y]);
 }
 
 // CRC-32 (PNG / zlib polynomial 0xEDB88320) of each 32 KiB IDAT chunk of
@@ -862,7 +480,7 @@ int png_tile(const uint8_t *filtered, size_t n_filtered, int w, int h, bool opq,
   s.avail_in = (uInt)n_filtered;
   s.next_out = z.data();
   s.avail_out = (uInt)z.size();
-  const int rc = deflate(&s, Z_FINISH);
+  const int rc = ::deflate(&s, Z_FINISH);   // zlib's, not the namespace of deflate_core.h
   const size_t zn = z.size() - s.avail_out;
   deflateEnd(&s);
   if (rc != Z_STREAM_END) return GSKYHIP_E_ARG;
@@ -951,9 +569,9 @@ int64_t gskyhip_png_workspace_size(int n_tiles, int max_w, int max_h) {
   const int64_t per = (int64_t)max_h * (1 + 4 * (int64_t)max_w);
   const int64_t a = ((int64_t)n_tiles * per + 255) / 256 * 256 + (int64_t)n_tiles * (8 + 8 + 4) + 1024;
   const int64_t b = ((int64_t)n_tiles * max_h * 4 + 255) / 256 * 256 + (int64_t)n_tiles * (4 + 8 + 8) + 1024 +
-                    (int64_t)n_tiles * (int64_t)sizeof(PngTab) + 256;
+                    (int64_t)n_tiles * (int64_t)sizeof(deflate::Plan) + 256;
   const int64_t c = (int64_t)n_tiles * per * 4 + (int64_t)n_tiles * max_h * 4 + 1024 +   // tokens, counts,
-                    (int64_t)n_tiles * kSymN * 4 + 256;                                  // symbol frequencies
+                    (int64_t)n_tiles * deflate::kSymN * 4 + 256;                                 // symbol frequencies
   return a + b + (int64_t)n_tiles * png_deflate_cap(per) + 1024 + c;
 }
 
@@ -962,6 +580,18 @@ int64_t gskyhip_png_bound(int width, int height) {
   const uLong raw = (uLong)height * (1 + 4 * (uLong)width);
   const uLong z = std::max<uLong>(compressBound(raw) + 64, (uLong)png_deflate_cap((int64_t)raw));
   return 8 + 25 + (int64_t)(z / 32768 + 1) * 12 + (int64_t)z + 12;
+}
+
+int gskyhip_png_deflate_rows_host(const uint8_t *rows, int h, int stride, int bpp, int fixed_only, uint8_t *out,
+                                  int64_t cap, int64_t *out_len) {
+  if (!rows || !out || !out_len || h <= 0 || stride <= 0 || (bpp != 3 && bpp != 4) || cap < 0 ||
+      (int64_t)h * stride > (1ll << 30))
+    return GSKYHIP_E_ARG;
+  try {
+    return deflate::encode_rows_host(rows, h, stride, bpp, fixed_only ? 1 : 0, out, cap, out_len);
+  } catch (...) {
+    return GSKYHIP_E_ARG;
+  }
 }
 
 int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, int64_t tile_stride,
@@ -1011,7 +641,7 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
     uint32_t *d_adler = (uint32_t *)b;
     int64_t *d_zlen = (int64_t *)(b + (((int64_t)n_tiles * 4 + 7) & ~(int64_t)7));
     int64_t *d_zoff = d_zlen + n_tiles;
-    PngTab *d_tab = (PngTab *)(((uintptr_t)(d_zoff + n_tiles) + 255) & ~(uintptr_t)255);
+    deflate::Plan *d_tab = (deflate::Plan *)(((uintptr_t)(d_zoff + n_tiles) + 255) & ~(uintptr_t)255);
     uint8_t *d_packed = (uint8_t *)(((uintptr_t)(d_tab + n_tiles) + 255) & ~(uintptr_t)255);
     // per-tile dynamic Huffman codes where they are shorter (GSKYHIP_PNG_FIXED=1: fixed codes only)
     const char *fx = std::getenv("GSKYHIP_PNG_FIXED");
@@ -1020,8 +650,8 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
                                    ~(uintptr_t)255);
     int32_t *d_ntok = (int32_t *)(d_tok + (int64_t)n_tiles * per);
     uint32_t *d_freq = (uint32_t *)(((uintptr_t)(d_ntok + (int64_t)n_tiles * max_h) + 255) & ~(uintptr_t)255);
-    if ((char *)(d_freq + (int64_t)n_tiles * kSymN) > ws + workspace_bytes) return GSKYHIP_E_ARG;
-    if (hipMemsetAsync(d_freq, 0, (size_t)n_tiles * kSymN * 4, s) != hipSuccess) return GSKYHIP_E_HIP;
+    if ((char *)(d_freq + (int64_t)n_tiles * deflate::kSymN) > ws + workspace_bytes) return GSKYHIP_E_ARG;
+    if (hipMemsetAsync(d_freq, 0, (size_t)n_tiles * deflate::kSymN * 4, s) != hipSuccess) return GSKYHIP_E_HIP;
     hipLaunchKernelGGL(png_tokenize_kernel, dim3((unsigned)((int64_t)n_tiles * ((max_h + 63) / 64))), dim3(64), 0, s, filt,
                        d_off, d_wh, d_opq, max_h, d_tok, d_ntok, per, d_freq, dynamic);
     hipLaunchKernelGGL(png_deflate_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, filt, d_off, d_wh, d_opq,
@@ -1044,8 +674,8 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
     if (hipMemcpyAsync(d_zoff, zoff.data(), (size_t)n_tiles * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(d_packed, 0, (size_t)std::max<int64_t>(total, 4), s) != hipSuccess)
       return GSKYHIP_E_HIP;
-    hipLaunchKernelGGL(png_deflate_write_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, filt, d_off, d_wh, d_opq,
-                       max_h, d_rowbits, d_adler, d_zoff, d_zlen, d_packed, d_tab, d_tok, d_ntok, per);
+    hipLaunchKernelGGL(png_deflate_write_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, d_wh, d_opq, max_h,
+                       d_rowbits, d_adler, d_zoff, d_packed, d_tab, d_tok, d_ntok, per);
     // IDAT CRCs behind the packed streams (the pinned read-back holds both)
     const int64_t crc_at = (total + 255) & ~(int64_t)255;
     const int64_t n_crc = (int64_t)n_tiles * max_chunks;

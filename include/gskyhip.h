@@ -807,6 +807,14 @@ int64_t gskyhip_png_bound(int width, int height);
 int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, int64_t tile_stride,
                        int64_t row_stride, const int32_t *sizes, void *workspace, int64_t workspace_bytes,
                        uint8_t *png_out, int64_t png_capacity, int64_t *png_sizes, int n_threads, void *stream);
+/* The host twin of gskyhip_encode_png's GPU deflate, for tests and tools (no
+ * product path calls it): the zlib stream of h rows of `stride` filtered bytes
+ * (HOST; the filter byte included, bpp 3 or 4 bytes a pixel) from the functions
+ * the kernels run, so the same bytes.  fixed_only: as GSKYHIP_PNG_FIXED=1.
+ * *out_len is the stream's length; GSKYHIP_INFLATE_E_CAP (nothing written)
+ * when it exceeds cap. */
+int gskyhip_png_deflate_rows_host(const uint8_t *rows, int h, int stride, int bpp, int fixed_only, uint8_t *out,
+                                  int64_t cap, int64_t *out_len);
 
 /* EncodeGdalOpen + EncodeGdal for format "geotiff" (utils/ogc_encoders.go:
  * 277-450) of one WCS coverage held in HBM: a BigTIFF with the reference's

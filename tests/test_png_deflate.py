@@ -10,8 +10,13 @@ The reference of every case is CPU-only: oracle.go_png_rows, zlib's inflate
 and PIL.  deflate_header() below reads the block header of a stream so a test
 can tell which path and which codes produced it.
 
-Recorded, not asserted (test_size_table prints it at -s): bytes of the default
-path's zlib stream on an MI355X against len(zlib.compress(rows, 6)).
+The bytes themselves are held to tests/golden/png_streams.json, recorded on an
+MI355X at the last commit whose PNG encoder was a copy of its own: the host
+twin gskyhip_png_deflate_rows_host on the CPU, the kernels inside check_case.
+
+Recorded (test_size_table prints it at -s; the gpu column is what the golden
+file pins): bytes of the default path's zlib stream on an MI355X against
+len(zlib.compress(rows, 6)).
 
     case         w x h          rows      gpu  zlib -6  ratio
     tiny         1x1               4       12       12   1.00
@@ -41,8 +46,11 @@ internal nodes past the length limit: every tree more than one level too deep
 came out incomplete and the tile fell back to the fixed codes.  Its code-length
 code was 5 bits deep; a 7-bit one was never seen.
 """
+import hashlib
 import heapq
 import io
+import json
+import os
 import zlib
 from fractions import Fraction
 
@@ -52,6 +60,15 @@ import pytest
 from .test_png import _check, _chunks
 
 E_ARG = -1   # GSKYHIP_E_ARG (include/gskyhip.h)
+
+# lengths and SHA-256 of the streams of both Deflate encoders at the commit
+# before they shared deflate_core.h (tests/golden/make_png_streams.py)
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "png_streams.json")) as _f:
+    GOLDEN = json.load(_f)
+
+
+def record(stream):
+    return {"len": len(stream), "sha256": hashlib.sha256(stream).hexdigest()}
 
 
 # ------------------------------------------------------------------ header reader
@@ -386,7 +403,10 @@ def check_case(name, enc, ref, mode="default", path="gpu"):
     tiles = tiles_of(name)
     pngs = enc(name, mode)
     assert len(pngs) == len(tiles)
-    return [check_tile(p, t, ref, path) for p, t in zip(pngs, tiles)]
+    out = [check_tile(p, t, ref, path) for p, t in zip(pngs, tiles)]
+    if mode in GOLDEN["png"] and path == "gpu":   # the bytes are the recorded ones
+        assert [record(z) for z, _, _ in out] == GOLDEN["png"][mode][name]
+    return out
 
 
 def filter_types(rows, h):
@@ -470,6 +490,58 @@ def test_window_tiles_meet_their_preconditions(oracle):
             assert s == 11201 and 3 * s > 32768 and r[2][:half] == r[0][:half] and r[3][half:] == r[0][half:]
         else:
             assert 3 * s == 24573 and r[3] == r[0] and r[1] != r[0] and r[2] != r[0]
+
+
+def host_twin_stream(rgba, ref, fixed):
+    """gskyhip_png_deflate_rows_host over the reference rows of a tile."""
+    import ctypes as C
+
+    from gsky_amd import lib
+    opaque, rows = ref.go_png_rows(rgba)
+    h = rgba.shape[0]
+    src = np.frombuffer(rows, np.uint8).copy()
+    out = np.empty(gpu_size_cap(len(rows)), np.uint8)
+    n = C.c_int64(-1)
+    rc = lib().gskyhip_png_deflate_rows_host(C.c_void_p(src.ctypes.data), h, len(rows) // h, 3 if opaque else 4,
+                                             int(fixed), C.c_void_p(out.ctypes.data), out.size, C.byref(n))
+    assert rc == 0
+    return out[:n.value].tobytes()
+
+
+@pytest.mark.parametrize("mode", ["default", "fixed"])
+def test_host_twin_gives_the_recorded_streams(ref, mode):
+    """The functions the PNG kernels run, on the host, give the bytes the GPU
+    gave before the encoders were merged -- every case but rows_4097 (host
+    zlib), in both modes."""
+    assert set(GOLDEN["png"][mode]) == set(CASES) - {"rows_4097"}
+    for name, recs in GOLDEN["png"][mode].items():
+        got = [host_twin_stream(t, ref, mode == "fixed") for t in tiles_of(name)]
+        assert [record(z) for z in got] == recs, name
+        for z, t in zip(got, tiles_of(name)):
+            assert zlib.decompress(z) == ref.go_png_rows(t)[1]
+            assert z[:2] == b"\x78\x01" and deflate_header(z)["btype"] in ((1,) if mode == "fixed" else (1, 2))
+    (one_row,), tiny = GOLDEN["png"]["default"]["one_row"], GOLDEN["png"]["default"]["tiny"]
+    assert one_row["len"] == 959   # a stored block would take 912
+    assert [r["len"] for r in tiny] == [12, 11, 13, 15, 18, 20]
+
+
+def test_tiny_tiles_take_the_fixed_fallback_on_the_host_twin(ref):
+    for t in tiles_of("tiny"):
+        assert deflate_header(host_twin_stream(t, ref, False))["btype"] == 1
+
+
+def test_block_encoder_gives_the_recorded_streams():
+    """gskyhip_deflate_blocks_host over tests/deflate_corpus.py: the bytes of
+    the commit before plan_block was split."""
+    from gsky_amd import encode
+
+    from .deflate_corpus import corpus
+    modes = {"zlib6": (True, 6), "raw6": (False, 6), "zlib0": (True, 0), "raw0": (False, 0)}
+    assert set(GOLDEN["deflate_host"]) == set(modes)
+    names, blocks = [n for n, _ in corpus()], [b for _, b in corpus()]
+    for mode, (wrapper, level) in modes.items():
+        streams = encode.deflate_blocks(blocks, zlib_wrapper=wrapper, level=level, where="host")
+        assert [dict(record(z), name=n) for n, z in zip(names, streams)] == GOLDEN["deflate_host"][mode], mode
 
 
 # ------------------------------------------------------------------ GPU cases, default path

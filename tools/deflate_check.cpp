@@ -9,6 +9,9 @@
 // input is allocated at exactly its length and the output at exactly the
 // capacity handed to the encoder, so the sanitizer sees any access past them.
 // The Fibonacci-weighted block must have driven the code-length limiter.
+// The PNG encoder's row path (encode_rows_host) runs over a constant, a noise
+// and an upsampled buffer, rows of one byte and one row of three bytes, with 3
+// and 4 bytes a pixel, under the same requirements.
 #include <zlib.h>
 
 #include <cstdint>
@@ -105,7 +108,61 @@ static int check_block(const std::string &name, const Bytes &src, int wrapper, i
   return limited;
 }
 
+// The PNG encoder's row path (encode_rows_host) over h rows of `stride` bytes,
+// with 3 and 4 bytes a pixel, default and fixed codes only: the same checks,
+// the output at exactly the 9 bits a byte no stream of that path exceeds.
+static void check_rows(const std::string &name, const Bytes &src, int h, int stride) {
+  uint8_t *in = (uint8_t *)std::malloc(src.size());
+  std::memcpy(in, src.data(), src.size());
+  const int64_t n = (int64_t)src.size(), cap = 2 + (3 + 9 * n + 7 + 7) / 8 + 4;
+  for (int bpp : {3, 4})
+    for (int fixed : {0, 1}) {
+      uint8_t *out = (uint8_t *)std::malloc((size_t)cap);
+      int64_t len = -1, len2 = -1;
+      int32_t status = gd::encode_rows_host(in, h, stride, bpp, fixed, out, cap, &len);
+      CHECK(status == gd::kOk && len > 0 && len <= cap, "status %d length %lld (bpp %d fixed %d)", (int)status,
+            (long long)len, bpp, fixed);
+      bool ok = false;
+      const Bytes back = zlib_inflate(out, (size_t)len, src.size(), false, &ok);
+      CHECK(ok && back == src, "zlib does not give the rows back (bpp %d fixed %d)", bpp, fixed);
+      const int btype = (out[2] >> 1) & 3;   // never stored; fixed where asked for
+      CHECK(out[0] == 0x78 && out[1] == 0x01 && (out[2] & 1) == 1 && (btype == 1 || (btype == 2 && !fixed)),
+            "not one final Huffman-coded block (BTYPE %d, bpp %d fixed %d)", btype, bpp, fixed);
+      uint8_t *exact = (uint8_t *)std::malloc((size_t)len);
+      status = gd::encode_rows_host(in, h, stride, bpp, fixed, exact, len, &len2);
+      CHECK(status == gd::kOk && len2 == len && std::memcmp(exact, out, (size_t)len) == 0, "not deterministic");
+      Bytes small((size_t)(len - 1), 0xA5);
+      status = gd::encode_rows_host(in, h, stride, bpp, fixed, small.data(), len - 1, &len2);
+      CHECK(status == gd::kOutputFull && len2 == len, "capacity %lld accepted", (long long)(len - 1));
+      for (uint8_t v : small) CHECK(v == 0xA5, "a refused stream was written");
+      std::free(exact);
+      std::free(out);
+    }
+  std::free(in);
+}
+
+static int check_png_rows() {
+  const int h = 16, stride = 121;   // 1 + 3 * 40 = 1 + 4 * 30
+  check_rows("rows_constant", Bytes((size_t)(h * stride), 7), h, stride);
+  check_rows("rows_noise", random_bytes((size_t)(h * stride)), h, stride);
+  for (int bpp : {3, 4}) {   // pixels and rows repeated four times, behind a filter byte
+    const int w = 40, s = 1 + bpp * w;
+    Bytes b((size_t)(h * s), 0);
+    const Bytes px = random_bytes((size_t)((h / 4) * (w / 4) * bpp));
+    for (int y = 0; y < h; y++)
+      for (int x = 0; x < w; x++)
+        for (int c = 0; c < bpp; c++) b[(size_t)(y * s + 1 + x * bpp + c)] = px[(size_t)(((y / 4) * (w / 4) + x / 4) * bpp + c)];
+    check_rows("rows_upsampled" + std::to_string(bpp), b, h, s);
+  }
+  Bytes one(50);
+  for (auto &v : one) v = (uint8_t)(rnd() % 5);
+  check_rows("rows_of_one_byte", one, 50, 1);
+  check_rows("one_row_of_three", Bytes{1, 2, 3}, 1, 3);
+  return 6;
+}
+
 int main() {
+  const int n_rows = check_png_rows();
   std::vector<std::pair<std::string, Bytes>> corpus;
   for (int n = 0; n <= 4; n++) {
     Bytes b;
@@ -180,6 +237,6 @@ int main() {
     std::printf("deflate_check: %d failures\n", fails);
     return 1;
   }
-  std::printf("deflate_check ok: %zu blocks\n", corpus.size());
+  std::printf("deflate_check ok: %zu blocks, %d row buffers\n", corpus.size(), n_rows);
   return 0;
 }
