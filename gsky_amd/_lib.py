@@ -129,6 +129,7 @@ EXPORTS = [
     "gskyhip_netcdf_read_decode", "gskyhip_register_geotiff_decode", "gskyhip_register_netcdf_decode",
     "gskyhip_deflate_bound", "gskyhip_deflate_workspace_size", "gskyhip_deflate_blocks", "gskyhip_deflate_blocks_host",
     "gskyhip_encode_netcdf_deflate", "gskyhip_png_deflate_rows_host",
+    "gskyhip_geotiff_bound_opts", "gskyhip_encode_geotiff_opts", "gskyhip_encode_geotiff_host",
 ]
 
 DECODE_HOST, DECODE_DEVICE = 0, 1
@@ -274,6 +275,15 @@ def lib() -> C.CDLL:
     L.gskyhip_geotiff_bound.restype = i64
     L.gskyhip_encode_geotiff.argtypes = [C.POINTER(vp), ci, ci, ci, ci, C.POINTER(d), ci, vp,
                                          C.POINTER(C.c_char_p), ci, ci, vp, i64, vp, i64, C.POINTER(i64), vp]
+    if hasattr(L, "gskyhip_encode_geotiff_opts"):   # absent from kept earlier builds (GSKYHIP_LIB=<name>)
+        L.gskyhip_geotiff_bound_opts.argtypes = [ci, ci, ci, ci, ci, ci, ci]
+        L.gskyhip_geotiff_bound_opts.restype = i64
+        L.gskyhip_encode_geotiff_opts.argtypes = [C.POINTER(vp), ci, ci, ci, ci, C.POINTER(d), ci, vp,
+                                                  C.POINTER(C.c_char_p), ci, ci, ci, ci, ci, ci, ci, ci, vp, i64,
+                                                  C.POINTER(i64), vp, vp]
+        L.gskyhip_encode_geotiff_host.argtypes = [C.POINTER(vp), ci, ci, ci, ci, C.POINTER(d), ci, vp,
+                                                  C.POINTER(C.c_char_p), ci, ci, ci, ci, ci, ci, vp, i64,
+                                                  C.POINTER(i64)]
     if hasattr(L, "gskyhip_encode_netcdf"):   # (an older A/B library for timing comparisons lacks it)
         L.gskyhip_netcdf_bound.argtypes = [ci, ci, ci, ci]
         L.gskyhip_netcdf_bound.restype = i64

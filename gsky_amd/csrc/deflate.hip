@@ -1,6 +1,7 @@
 // deflate.hip -- independent blocks deflated on the GPU, the
-// same encoder on host threads, and the netCDF writer's chunk preparation
-// (shuffle) and packing around it.
+// same encoder on host threads, and the block preparation and packing of its
+// two coverage writers around it: the netCDF writer's chunks (shuffle) and
+// the GeoTIFF writer's tiles (edge padding and the TIFF predictor).
 //
 // The encoder is deflate_core.h, compiled for both sides.  On the device:
 //   * deflate_tokenize_kernel, a wave per 64 segments of a block, a lane per
@@ -26,6 +27,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cstdint>
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -33,6 +35,7 @@
 #include "../../include/gskyhip.h"
 #include "deflate.h"
 #include "deflate_core.h"
+#include "tiffwrite.h"
 
 namespace gsky {
 namespace {
@@ -287,6 +290,62 @@ __global__ __launch_bounds__(64) void nc_pack_copy_kernel(const uint8_t *__restr
   for (int64_t j = threadIdx.x; j < L; j += 64) dst[j] = src[j];
 }
 
+// ---------------------------------------------------------------- GeoTIFF tiles
+template <int SS> struct SampleOf;
+template <> struct SampleOf<1> { typedef uint8_t type; };
+template <> struct SampleOf<2> { typedef uint16_t type; };
+template <> struct SampleOf<4> { typedef uint32_t type; };
+
+// the bits of sample (gx, gy) of the band, `pad` outside the image (or without a band)
+template <int SS>
+__device__ __forceinline__ uint32_t tiff_sample_at(const uint8_t *__restrict__ band, int width, int height, int gx,
+                                                   int gy, uint32_t pad) {
+  typedef typename SampleOf<SS>::type T;
+  if (!band || gx >= width || gy >= height) return pad;
+  return (uint32_t)((const T *)band)[(int64_t)gy * width + gx];
+}
+
+// Tiles [tile0, tile0 + gridDim.y) of a band (row-major over ntx columns of
+// tiles) as the compressor receives them, tile k at dst + k * tile_bytes:
+// block_y rows of block_x samples of SS bytes, edge tiles padded, the TIFF
+// predictor PRED applied.  PRED 1, 2: a thread per sample (2: its difference
+// to the left neighbour in the tile row, wrapping in the sample width; the
+// first kept).  PRED 3 (SS = 4): a thread per output byte i = p * block_x + x
+// of a row -- byte 3 - p of sample x (the planes most significant first)
+// minus the byte before it in the row, which at x = 0 is the last column of
+// plane p - 1; byte 0 is kept.  Reads are coalesced along x, writes are
+// consecutive.  `items` = threads a tile needs (< 2^31).
+template <int SS, int PRED>
+__global__ __launch_bounds__(256) void tiff_tile_predict_kernel(const uint8_t *__restrict__ band, int width,
+                                                                int height, int block_x, int block_y, int ntx,
+                                                                int64_t tile0, uint32_t items, uint32_t pad,
+                                                                uint8_t *__restrict__ dst) {
+  typedef typename SampleOf<SS>::type T;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= items) return;
+  const int64_t tile = tile0 + blockIdx.y;
+  const int tx = (int)(tile % ntx), ty = (int)(tile / ntx);
+  const int64_t tile_bytes = (int64_t)block_x * block_y * SS;
+  uint8_t *out = dst + (int64_t)blockIdx.y * tile_bytes;
+  if (PRED == 3) {
+    const uint32_t row_bytes = 4u * (uint32_t)block_x;
+    const uint32_t r = i / row_bytes, c = i - r * row_bytes;
+    const uint32_t p = c / (uint32_t)block_x, x = c - p * (uint32_t)block_x;
+    const int gy = ty * block_y + (int)r, gx0 = tx * block_x;
+    const uint32_t cur = (tiff_sample_at<SS>(band, width, height, gx0 + (int)x, gy, pad) >> (8 * (3 - p))) & 0xFFu;
+    uint32_t prev = 0;
+    if (x > 0) prev = (tiff_sample_at<SS>(band, width, height, gx0 + (int)x - 1, gy, pad) >> (8 * (3 - p))) & 0xFFu;
+    else if (p > 0) prev = (tiff_sample_at<SS>(band, width, height, gx0 + block_x - 1, gy, pad) >> (8 * (4 - p))) & 0xFFu;
+    out[i] = (uint8_t)(cur - prev);
+  } else {
+    const uint32_t r = i / (uint32_t)block_x, x = i - r * (uint32_t)block_x;
+    const int gy = ty * block_y + (int)r, gx = tx * block_x + (int)x;
+    uint32_t v = tiff_sample_at<SS>(band, width, height, gx, gy, pad);
+    if (PRED == 2 && x > 0) v -= tiff_sample_at<SS>(band, width, height, gx - 1, gy, pad);
+    ((T *)out)[i] = (T)v;
+  }
+}
+
 struct NcLayout {
   int64_t chunks, z, off, packed, dws, end, zstride;
 };
@@ -303,7 +362,95 @@ NcLayout nc_layout(int64_t row_bytes, int rows) {
   return N;
 }
 
+// The n blocks of block_bytes each at ws + N.chunks (N = nc_layout(block_bytes,
+// n)) deflated into zlib streams and packed end to end at ws + N.packed:
+// lens[k] = the length of stream k, *total their sum.  Two small copies
+// (lengths, statuses) and a synchronise; a block whose status is not OK fails
+// the slab.
+int deflate_pack_slab(const NcLayout &N, int64_t block_bytes, int n, int level, uint8_t *ws, int64_t ws_bytes,
+                      int64_t *lens, int64_t *total, hipStream_t s) {
+  std::vector<int64_t> in_off((size_t)n), in_len((size_t)n, block_bytes), out_off((size_t)n),
+      out_cap((size_t)n, N.zstride);
+  for (int k = 0; k < n; k++) {
+    in_off[k] = (int64_t)k * block_bytes;
+    out_off[k] = (int64_t)k * N.zstride;
+  }
+  std::vector<uint8_t> host_buf;
+  Layout L;
+  int rc = deflate_launch(ws + N.chunks, in_off.data(), in_len.data(), n, ws + N.z, out_off.data(), out_cap.data(), 1,
+                          level, ws + N.dws, ws_bytes - N.dws, s, host_buf, L);
+  const int64_t *d_len = (const int64_t *)(ws + N.dws + L.out_len);
+  int64_t *d_off = (int64_t *)(ws + N.off);
+  if (!rc) {
+    hipLaunchKernelGGL(nc_pack_scan_kernel, dim3(1), dim3(256), 0, s, d_len, n, d_off);
+    hipLaunchKernelGGL(nc_pack_copy_kernel, dim3((unsigned)n), dim3(64), 0, s, ws + N.z, N.zstride, d_len, d_off, n,
+                       ws + N.packed);
+    if (hipGetLastError() != hipSuccess) rc = GSKYHIP_E_HIP;
+  }
+  std::vector<int32_t> st((size_t)n);
+  if (!rc && (hipMemcpyAsync(lens, d_len, 8 * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess ||
+              hipMemcpyAsync(st.data(), ws + N.dws + L.status, 4 * (size_t)n, hipMemcpyDeviceToHost, s) != hipSuccess))
+    rc = GSKYHIP_E_HIP;
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = GSKYHIP_E_HIP;   // host_buf must outlive its upload
+  if (rc) return rc;
+  *total = 0;
+  for (int k = 0; k < n; k++) {
+    if (st[k] != GSKYHIP_INFLATE_OK || lens[k] <= 0 || lens[k] > N.zstride) return GSKYHIP_E_HIP;
+    *total += lens[k];
+  }
+  return GSKYHIP_OK;
+}
+
 }  // namespace
+
+int tiff_slab_tiles(int64_t tile_bytes, int64_t tiles_per_band, int slab_tiles) {
+  int64_t t = slab_tiles > 0 ? slab_tiles : std::max<int64_t>(1, tiff::kSlabRawBytes / std::max<int64_t>(1, tile_bytes));
+  t = std::min<int64_t>(t, tiff::kSlabMaxTiles);
+  return (int)std::min<int64_t>(t, tiles_per_band);
+}
+
+int64_t tiff_deflate_workspace(int64_t tile_bytes, int tiles) { return nc_layout(tile_bytes, tiles).end; }
+
+int tiff_deflate_slab(const void *dev_band, int ts, int predictor, int width, int height, int block_x, int block_y,
+                      int ntx, int64_t tile0, int tiles, uint32_t pad, int level, uint8_t *ws, int64_t ws_bytes,
+                      uint8_t *dst, int64_t dst_cap, int64_t *lens, int64_t *copied, hipStream_t s) {
+  const int64_t tile_bytes = (int64_t)block_x * block_y * ts;
+  if (width <= 0 || height <= 0 || block_x <= 0 || block_y <= 0 || ntx <= 0 || tile0 < 0 || tiles <= 0 ||
+      tiles > tiff::kSlabMaxTiles || tile_bytes > tiff::kMaxTileBytes || !dst || !lens)
+    return GSKYHIP_E_ARG;
+  const int64_t nty = ((int64_t)height + block_y - 1) / block_y;
+  // the tiles lie in the band's grid, and pixel coordinates of padded tiles stay below 2^31
+  if ((int64_t)ntx * block_x > INT32_MAX || nty * block_y > INT32_MAX || tile0 + tiles > ntx * nty)
+    return GSKYHIP_E_ARG;
+  const NcLayout N = nc_layout(tile_bytes, tiles);
+  if (!ws || ws_bytes < N.end) return GSKYHIP_E_ARG;
+  const uint32_t items = (uint32_t)(predictor == 3 ? tile_bytes : tile_bytes / ts);
+  const dim3 grid((items + 255u) / 256u, (unsigned)tiles);
+  const uint8_t *band = (const uint8_t *)dev_band;
+  uint8_t *raw = ws + N.chunks;
+#define GSKY_TIFF_PREDICT(SS, PRED)                                                                             \
+  hipLaunchKernelGGL((tiff_tile_predict_kernel<SS, PRED>), grid, dim3(256), 0, s, band, width, height, block_x, \
+                     block_y, ntx, tile0, items, pad, raw)
+  if (predictor == 3 && ts == 4) GSKY_TIFF_PREDICT(4, 3);
+  else if (predictor == 2 && ts == 4) GSKY_TIFF_PREDICT(4, 2);
+  else if (predictor == 2 && ts == 2) GSKY_TIFF_PREDICT(2, 2);
+  else if (predictor == 2 && ts == 1) GSKY_TIFF_PREDICT(1, 2);
+  else if (predictor == 1 && ts == 4) GSKY_TIFF_PREDICT(4, 1);
+  else if (predictor == 1 && ts == 2) GSKY_TIFF_PREDICT(2, 1);
+  else if (predictor == 1 && ts == 1) GSKY_TIFF_PREDICT(1, 1);
+  else return GSKYHIP_E_ARG;
+#undef GSKY_TIFF_PREDICT
+  if (hipGetLastError() != hipSuccess) return GSKYHIP_E_HIP;
+  int64_t total = 0;
+  const int rc = deflate_pack_slab(N, tile_bytes, tiles, level, ws, ws_bytes, lens, &total, s);
+  if (rc) return rc;
+  if (total > dst_cap) return GSKYHIP_E_ARG;
+  if (hipMemcpyAsync(dst, ws + N.packed, (size_t)total, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return GSKYHIP_E_HIP;
+  if (copied) *copied += total;
+  return GSKYHIP_OK;
+}
 
 int nc_slab_rows(int64_t row_bytes, int height, int slab_rows) {
   int64_t r = slab_rows > 0 ? slab_rows : std::max<int64_t>(1, kNcSlabRawBytes / std::max<int64_t>(1, row_bytes));
@@ -335,36 +482,10 @@ int nc_deflate_slab(const void *dev_band, int src_size, int elem_size, int width
   else
     return GSKYHIP_E_ARG;
   if (hipGetLastError() != hipSuccess) return GSKYHIP_E_HIP;
-  std::vector<int64_t> in_off((size_t)rows), in_len((size_t)rows, row_bytes), out_off((size_t)rows),
-      out_cap((size_t)rows, N.zstride);
-  for (int k = 0; k < rows; k++) {
-    in_off[k] = (int64_t)k * row_bytes;
-    out_off[k] = (int64_t)k * N.zstride;
-  }
-  std::vector<uint8_t> host_buf;
-  Layout L;
-  int rc = deflate_launch(chunks, in_off.data(), in_len.data(), rows, ws + N.z, out_off.data(), out_cap.data(), 1,
-                          level, ws + N.dws, ws_bytes - N.dws, s, host_buf, L);
-  const int64_t *d_len = (const int64_t *)(ws + N.dws + L.out_len);
-  int64_t *d_off = (int64_t *)(ws + N.off);
-  if (!rc) {
-    hipLaunchKernelGGL(nc_pack_scan_kernel, dim3(1), dim3(256), 0, s, d_len, rows, d_off);
-    hipLaunchKernelGGL(nc_pack_copy_kernel, dim3((unsigned)rows), dim3(64), 0, s, ws + N.z, N.zstride, d_len, d_off,
-                       rows, ws + N.packed);
-    if (hipGetLastError() != hipSuccess) rc = GSKYHIP_E_HIP;
-  }
   std::vector<int64_t> lens((size_t)rows);
-  std::vector<int32_t> st((size_t)rows);
-  if (!rc && (hipMemcpyAsync(lens.data(), d_len, 8 * (size_t)rows, hipMemcpyDeviceToHost, s) != hipSuccess ||
-              hipMemcpyAsync(st.data(), ws + N.dws + L.status, 4 * (size_t)rows, hipMemcpyDeviceToHost, s) != hipSuccess))
-    rc = GSKYHIP_E_HIP;
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = GSKYHIP_E_HIP;   // host_buf must outlive its upload
-  if (rc) return rc;
   int64_t total = 0;
-  for (int k = 0; k < rows; k++) {
-    if (st[k] != GSKYHIP_INFLATE_OK || lens[k] <= 0 || lens[k] > N.zstride) return GSKYHIP_E_HIP;
-    total += lens[k];
-  }
+  const int rc = deflate_pack_slab(N, row_bytes, rows, level, ws, ws_bytes, lens.data(), &total, s);
+  if (rc) return rc;
   std::vector<uint8_t> packed((size_t)total);
   if (hipMemcpyAsync(packed.data(), ws + N.packed, (size_t)total, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)

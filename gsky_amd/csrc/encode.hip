@@ -39,7 +39,9 @@
 #include <vector>
 
 #include "../../include/gskyhip.h"
+#include "deflate.h"
 #include "deflate_core.h"
+#include "tiffwrite.h"
 
 namespace gsky {
 namespace {
@@ -356,34 +358,6 @@ __global__ __launch_bounds__(256) void png_idat_crc_kernel(const uint8_t *__rest
 }
 
 // ------------------------------------------------------------------ GeoTIFF
-// PackBits (TIFF 6.0 section 9) of one tile row (libtiff encodes tiled
-// PackBits row by row): runs of 3+ equal bytes as replicate runs, the rest
-// as literal runs, at most 128 bytes each.  Returns the encoded length.
-__device__ int packbits_row(const uint8_t *in, int n, uint8_t *out) {
-  int i = 0, o = 0;
-  while (i < n) {
-    int run = 1;
-    while (i + run < n && run < 128 && in[i + run] == in[i]) run++;
-    if (run >= 3) {
-      out[o++] = (uint8_t)(257 - run);   // -(run - 1)
-      out[o++] = in[i];
-      i += run;
-      continue;
-    }
-    // literal: up to the next run of 3 (or 128 bytes)
-    int j = i, lit = 0;
-    while (j < n && lit < 128) {
-      if (j + 2 < n && in[j] == in[j + 1] && in[j] == in[j + 2]) break;
-      j++;
-      lit++;
-    }
-    out[o++] = (uint8_t)(lit - 1);
-    for (int k = 0; k < lit; k++) out[o++] = in[i + k];
-    i += lit;
-  }
-  return o;
-}
-
 // One thread per (band, tile, row of the tile): the row's samples (edge
 // tiles padded with `pad`) PackBits-encoded into its slot.
 __global__ __launch_bounds__(256) void tiff_rows_kernel(const uint8_t *const *__restrict__ bands, int ts, int width,
@@ -407,7 +381,7 @@ __global__ __launch_bounds__(256) void tiff_rows_kernel(const uint8_t *const *__
     const bool in = src && gx < width && y < height;   // no source: an EmptyTile band, all `pad`
     for (int k = 0; k < ts; k++) line[x * ts + k] = in ? src[((int64_t)y * width + gx) * ts + k] : pad[b * 8 + k];
   }
-  len[r] = packbits_row(line, rb, enc + r * slot);
+  len[r] = tiff::packbits_row(line, rb, enc + r * slot);
 }
 
 // ------------------------------------------------------------------ host framing
@@ -487,67 +461,6 @@ int png_tile(const uint8_t *filtered, size_t n_filtered, int w, int h, bool opq,
   for (size_t p = 0; p < zn; p += 32768) chunk(o, "IDAT", z.data() + p, std::min<size_t>(32768, zn - p));
   chunk(o, "IEND", nullptr, 0);
   return 0;
-}
-
-// BigTIFF writer state: IFD entries (sorted by tag on output) + out-of-line data.
-struct TiffEntry {
-  uint16_t tag, type;
-  uint64_t count;
-  std::vector<uint8_t> data;   // little-endian values
-};
-
-template <typename T> void put_le(std::vector<uint8_t> &o, T v) {
-  for (size_t k = 0; k < sizeof(T); k++) o.push_back((uint8_t)((uint64_t)v >> (8 * k)));
-}
-
-TiffEntry tiff_shorts(uint16_t tag, const std::vector<uint16_t> &v) {
-  TiffEntry e{tag, 3, v.size(), {}};
-  for (uint16_t x : v) put_le(e.data, x);
-  return e;
-}
-TiffEntry tiff_long(uint16_t tag, uint32_t v) {
-  TiffEntry e{tag, 4, 1, {}};
-  put_le(e.data, v);
-  return e;
-}
-TiffEntry tiff_long8s(uint16_t tag, const std::vector<uint64_t> &v) {
-  TiffEntry e{tag, 16, v.size(), {}};
-  for (uint64_t x : v) put_le(e.data, x);
-  return e;
-}
-TiffEntry tiff_doubles(uint16_t tag, const std::vector<double> &v) {
-  TiffEntry e{tag, 12, v.size(), {}};
-  for (double x : v) {
-    uint64_t u;
-    std::memcpy(&u, &x, 8);
-    put_le(e.data, u);
-  }
-  return e;
-}
-TiffEntry tiff_ascii(uint16_t tag, const std::string &s) {
-  TiffEntry e{tag, 2, s.size() + 1, {}};
-  e.data.assign(s.begin(), s.end());
-  e.data.push_back(0);
-  return e;
-}
-
-bool epsg_geographic(int epsg) {
-  return epsg == 4326 || epsg == 4283 || epsg == 4269 || epsg == 4258 || epsg == 4167 || epsg == 4674 ||
-         epsg == 7844;
-}
-
-std::string xml_escape(const char *s) {
-  std::string o;
-  for (; s && *s; s++) {
-    switch (*s) {
-      case '&': o += "&amp;"; break;
-      case '<': o += "&lt;"; break;
-      case '>': o += "&gt;"; break;
-      case '"': o += "&quot;"; break;
-      default: o += *s;
-    }
-  }
-  return o;
 }
 
 }  // namespace
@@ -751,21 +664,10 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
 }
 
 // ---- GeoTIFF (EncodeGdalOpen / EncodeGdal, utils/ogc_encoders.go:277-450)
-static int tiff_sample(int dtype, int &ts, uint16_t &fmt) {
-  switch (dtype) {
-    case GSKYHIP_BYTE: ts = 1; fmt = 1; return 0;
-    case GSKYHIP_SIGNEDBYTE: ts = 1; fmt = 2; return 0;
-    case GSKYHIP_INT16: ts = 2; fmt = 2; return 0;
-    case GSKYHIP_UINT16: ts = 2; fmt = 1; return 0;
-    case GSKYHIP_FLOAT32: ts = 4; fmt = 3; return 0;
-    default: return GSKYHIP_E_TYPE;
-  }
-}
-
 int64_t gskyhip_geotiff_workspace_size(int width, int height, int n_bands, int dtype, int block_x, int block_y) {
   int ts;
   uint16_t fmt;
-  if (width <= 0 || height <= 0 || n_bands <= 0 || block_x <= 0 || block_y <= 0 || tiff_sample(dtype, ts, fmt))
+  if (width <= 0 || height <= 0 || n_bands <= 0 || block_x <= 0 || block_y <= 0 || tiff::sample(dtype, ts, fmt))
     return 0;
   const int64_t ntx = (width + block_x - 1) / block_x, nty = (height + block_y - 1) / block_y;
   const int64_t rows = (int64_t)n_bands * ntx * nty * block_y;
@@ -774,31 +676,23 @@ int64_t gskyhip_geotiff_workspace_size(int width, int height, int n_bands, int d
   return rows * (rb + slot + 4) + 8 * (int64_t)n_bands + 64 * (int64_t)n_bands + 4096;
 }
 
-int64_t gskyhip_geotiff_bound(int width, int height, int n_bands, int dtype, int block_x, int block_y) {
-  int ts;
-  uint16_t fmt;
-  if (width <= 0 || height <= 0 || n_bands <= 0 || block_x <= 0 || block_y <= 0 || tiff_sample(dtype, ts, fmt))
-    return 0;
-  const int64_t ntx = (width + block_x - 1) / block_x, nty = (height + block_y - 1) / block_y;
-  const int64_t rows = (int64_t)n_bands * ntx * nty * block_y;
-  const int64_t rb = (int64_t)block_x * ts;
-  return rows * (rb + rb / 128 + 2) + (int64_t)n_bands * ntx * nty * 16 + 65536 + 512 * (int64_t)n_bands;
-}
-
+// (gskyhip_geotiff_bound, the band rules and the framing: tiffwrite.cpp)
 int gskyhip_encode_geotiff(const void *const *bands, int n_bands, int dtype, int width, int height,
                            const double *geot, int epsg, const double *nodata, const char *const *names,
                            int block_x, int block_y, void *workspace, int64_t workspace_bytes, uint8_t *out,
                            int64_t capacity, int64_t *size, void *stream) {
-  int ts;
-  uint16_t fmt;
   if (!bands || !geot || !out || !size || n_bands <= 0 || n_bands > 4096) return GSKYHIP_E_ARG;
-  if (tiff_sample(dtype, ts, fmt)) return GSKYHIP_E_TYPE;
-  if (width <= 0 || height <= 0 || block_x <= 0 || block_y <= 0 || block_x % 16 || block_y % 16) return GSKYHIP_E_ARG;
+  tiff::Spec sp;
+  sp.n_bands = n_bands; sp.dtype = dtype; sp.width = width; sp.height = height;
+  sp.geot = geot; sp.epsg = epsg; sp.nodata = nodata; sp.names = names;
+  sp.block_x = block_x; sp.block_y = block_y;
+  const int bad = sp.check();
+  if (bad) return bad;
   if (!workspace || workspace_bytes < gskyhip_geotiff_workspace_size(width, height, n_bands, dtype, block_x, block_y))
     return GSKYHIP_E_ARG;
   if (capacity < gskyhip_geotiff_bound(width, height, n_bands, dtype, block_x, block_y)) return GSKYHIP_E_ARG;
-  const int ntx = (width + block_x - 1) / block_x, nty = (height + block_y - 1) / block_y;
-  const int64_t n_tiles = (int64_t)n_bands * ntx * nty;
+  const int ts = sp.ts, ntx = sp.ntx, nty = sp.nty;
+  const int64_t n_tiles = sp.n_tiles();
   const int64_t n_rows = n_tiles * block_y;
   const int64_t rb = (int64_t)block_x * ts;
   const int64_t slot = rb + rb / 128 + 2;
@@ -808,27 +702,12 @@ int gskyhip_encode_geotiff(const void *const *bands, int n_bands, int dtype, int
   int32_t *len = (int32_t *)(enc + n_rows * slot);
   const uint8_t **d_bands = (const uint8_t **)(((uintptr_t)(len + n_rows) + 15) & ~(uintptr_t)15);
   uint8_t *d_pad = (uint8_t *)(d_bands + n_bands);
-  // EncodeGdal (ogc_encoders.go:357-436) skips EmptyTile bands: no nodata, no
-  // long_name, no pixels -- GTiff fills their blocks at close with the
-  // dataset nodata, the last value SetNoDataValue stored (one per GeoTIFF).
-  std::vector<char> empty((size_t)n_bands, 0);
-  int last_nd = -1;   // the band whose nodata the file keeps
-  for (int b = 0; b < n_bands; b++) {
-    empty[b] = names && names[b] && std::strncmp(names[b], "EmptyTile", 9) == 0;
-    if (!empty[b] && nodata) last_nd = b;
-  }
-  // edge-tile padding: the band's nodata in the band type (0 without one);
-  // an EmptyTile band is all the dataset nodata
+  // the band pointers (none for an EmptyTile band: all pad) and the pad samples in one upload
   std::vector<char> meta((size_t)n_bands * 8 + (size_t)n_bands * 8, 0);
   std::memcpy(meta.data(), bands, (size_t)n_bands * 8);
-  for (int b = 0; b < n_bands; b++) {
-    uint8_t *pb = (uint8_t *)meta.data() + (size_t)n_bands * 8 + 8 * b;
-    if (empty[b]) std::memset(meta.data() + 8 * (size_t)b, 0, 8);
-    const double v = empty[b] ? (last_nd >= 0 ? nodata[last_nd] : 0.0) : nodata ? nodata[b] : 0.0;
-    if (dtype == GSKYHIP_FLOAT32) { const float f = (float)v; std::memcpy(pb, &f, 4); }
-    else if (ts == 2) { const int16_t h = (int16_t)(dtype == GSKYHIP_UINT16 ? (int32_t)(uint16_t)v : (int32_t)v); std::memcpy(pb, &h, 2); }
-    else pb[0] = (uint8_t)(int)v;
-  }
+  for (int b = 0; b < n_bands; b++)
+    if (sp.empty[b]) std::memset(meta.data() + 8 * (size_t)b, 0, 8);
+  std::memcpy(meta.data() + (size_t)n_bands * 8, sp.pad.data(), (size_t)n_bands * 8);
   hipStream_t s = (hipStream_t)stream;
   if (hipMemcpyAsync(d_bands, meta.data(), meta.size(), hipMemcpyHostToDevice, s) != hipSuccess) return GSKYHIP_E_HIP;
   hipLaunchKernelGGL(tiff_rows_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, d_bands, ts, width,
@@ -841,92 +720,127 @@ int gskyhip_encode_geotiff(const void *const *bands, int n_bands, int dtype, int
       hipStreamSynchronize(s) != hipSuccess)
     return GSKYHIP_E_HIP;
   // file: header | tile data (band-major, tiles row-major) | IFD | out-of-line tag data
-  std::vector<uint8_t> o;
-  o.reserve((size_t)std::min<int64_t>(capacity, 1LL << 30));
-  o.push_back('I'); o.push_back('I');
-  put_le<uint16_t>(o, 43); put_le<uint16_t>(o, 8); put_le<uint16_t>(o, 0);
-  put_le<uint64_t>(o, 0);   // first IFD offset, patched below
-  std::vector<uint64_t> toff((size_t)n_tiles), tcnt((size_t)n_tiles);
+  tiff::Writer W(out, capacity, n_tiles);
   for (int64_t t = 0; t < n_tiles; t++) {
-    toff[t] = o.size();
+    W.begin_tile();
     for (int r = 0; r < block_y; r++) {
       const int64_t i = t * block_y + r;
-      o.insert(o.end(), encs.begin() + i * slot, encs.begin() + i * slot + lens[i]);
+      W.append(encs.data() + i * slot, lens[i]);
     }
-    tcnt[t] = o.size() - toff[t];
+    W.end_tile();
   }
-  if (o.size() & 1) o.push_back(0);
-  std::vector<TiffEntry> ents;
-  ents.push_back(tiff_long(256, (uint32_t)width));
-  ents.push_back(tiff_long(257, (uint32_t)height));
-  ents.push_back(tiff_shorts(258, std::vector<uint16_t>((size_t)n_bands, (uint16_t)(8 * ts))));
-  ents.push_back(tiff_shorts(259, {32773}));   // PackBits
-  // GTiff Create's default photometric: RGB for 3 or 4 Byte bands (the 4th
-  // an associated alpha extra sample), MinIsBlack otherwise
-  const bool byte = dtype == GSKYHIP_BYTE || dtype == GSKYHIP_SIGNEDBYTE;
-  const bool rgb = byte && (n_bands == 3 || n_bands == 4);
-  ents.push_back(tiff_shorts(262, {(uint16_t)(rgb ? 2 : 1)}));
-  ents.push_back(tiff_shorts(277, {(uint16_t)n_bands}));
-  ents.push_back(tiff_shorts(284, {(uint16_t)(n_bands > 1 ? 2 : 1)}));   // INTERLEAVE=BAND
-  ents.push_back(tiff_long(322, (uint32_t)block_x));
-  ents.push_back(tiff_long(323, (uint32_t)block_y));
-  ents.push_back(tiff_long8s(324, toff));
-  ents.push_back(tiff_long8s(325, tcnt));
-  if (rgb && n_bands == 4) ents.push_back(tiff_shorts(338, {1}));
-  else if (!rgb && n_bands > 1) ents.push_back(tiff_shorts(338, std::vector<uint16_t>((size_t)n_bands - 1, 0)));
-  ents.push_back(tiff_shorts(339, std::vector<uint16_t>((size_t)n_bands, fmt)));
-  if (geot[2] == 0.0 && geot[4] == 0.0) {
-    ents.push_back(tiff_doubles(33550, {geot[1], -geot[5], 0.0}));
-    ents.push_back(tiff_doubles(33922, {0.0, 0.0, 0.0, geot[0], geot[3], 0.0}));
-  } else {   // ModelTransformationTag for rotated grids
-    ents.push_back(tiff_doubles(34264, {geot[1], geot[2], 0.0, geot[0], geot[4], geot[5], 0.0, geot[3],
-                                        0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0}));
-  }
-  if (epsg > 0) {
-    const bool geo = epsg_geographic(epsg);
-    ents.push_back(tiff_shorts(34735, {1, 1, 0, 3, 1024, 0, 1, (uint16_t)(geo ? 2 : 1), 1025, 0, 1, 1,
-                                       (uint16_t)(geo ? 2048 : 3072), 0, 1, (uint16_t)epsg}));
-  }
-  if (names) {   // GDALSetMetadataItem("long_name", NameSpace) per band
-    std::string md = "<GDALMetadata>\n";
-    for (int b = 0; b < n_bands; b++)
-      if (names[b] && !empty[b])
-        md += "  <Item name=\"long_name\" sample=\"" + std::to_string(b) + "\">" + xml_escape(names[b]) + "</Item>\n";
-    md += "</GDALMetadata>";
-    ents.push_back(tiff_ascii(42112, md));
-  }
-  if (last_nd >= 0) {   // GDAL_NODATA: a single dataset value, the last band's that set one
-    char buf[64];
-    std::snprintf(buf, sizeof(buf), "%.18g", nodata[last_nd]);
-    ents.push_back(tiff_ascii(42113, buf));
-  }
-  std::sort(ents.begin(), ents.end(), [](const TiffEntry &a, const TiffEntry &b) { return a.tag < b.tag; });
-  const uint64_t ifd = o.size();
-  const uint64_t ifd_bytes = 8 + 20 * ents.size() + 8;
-  uint64_t extra = ifd + ifd_bytes;
-  std::vector<uint8_t> tail;
-  put_le<uint64_t>(o, ents.size());
-  for (auto &e : ents) {
-    put_le<uint16_t>(o, e.tag);
-    put_le<uint16_t>(o, e.type);
-    put_le<uint64_t>(o, e.count);
-    if (e.data.size() <= 8) {
-      std::vector<uint8_t> v = e.data;
-      v.resize(8, 0);
-      o.insert(o.end(), v.begin(), v.end());
-    } else {
-      put_le<uint64_t>(o, extra + tail.size());
-      tail.insert(tail.end(), e.data.begin(), e.data.end());
-      if (tail.size() & 1) tail.push_back(0);
+  return W.finish(sp, size);
+}
+
+// The Deflate file with the tiles predicted and deflated in HBM, a band at a
+// time in slabs of tiles (deflate.hip): each slab's packed streams are copied
+// straight to their place in the file.  A band without samples (EmptyTile, or
+// no pointer) is one tile compressed once by the encoder's host twin (the
+// same bytes) and repeated.
+static int encode_geotiff_device(const tiff::Spec &sp, const void *const *bands, int zlevel, int slab_tiles,
+                                 uint8_t *out, int64_t capacity, int64_t *size, int64_t *stats, hipStream_t s) {
+  const int64_t tpb = sp.tiles_per_band();
+  const int slab = tiff_slab_tiles(sp.tile_bytes, tpb, slab_tiles);
+  const int64_t ws_bytes = tiff_deflate_workspace(sp.tile_bytes, slab);
+  uint8_t *ws = nullptr;
+  if (hipMalloc((void **)&ws, (size_t)ws_bytes) != hipSuccess) return GSKYHIP_E_HIP;
+  int64_t st[4] = {0, 0, 0, ws_bytes};
+  tiff::Writer W(out, capacity, sp.n_tiles());
+  std::vector<int64_t> lens((size_t)slab);
+  std::vector<uint8_t> pad_z;
+  uint32_t pad_of = 0;
+  int rc = 0;
+  for (int b = 0; b < sp.n_bands && !rc; b++) {
+    const void *band = sp.empty[b] ? nullptr : bands[b];
+    if (!band) {
+      if (pad_z.empty() || pad_of != sp.pad_bits(b)) {
+        rc = tiff::deflate_tile(sp, nullptr, b, 0, 0, zlevel, pad_z);
+        pad_of = sp.pad_bits(b);
+      }
+      for (int64_t t = 0; t < tpb && !rc; t++) {
+        W.begin_tile();
+        W.append(pad_z.data(), (int64_t)pad_z.size());
+        W.end_tile();
+      }
+      continue;
     }
+    for (int64_t t0 = 0; t0 < tpb && !rc; t0 += slab) {
+      const int n = (int)std::min<int64_t>(slab, tpb - t0);
+      rc = tiff_deflate_slab(band, sp.ts, sp.predictor, sp.width, sp.height, sp.block_x, sp.block_y, sp.ntx, t0, n,
+                             sp.pad_bits(b), zlevel, ws, ws_bytes, W.cursor(), W.left(), lens.data(), &st[2], s);
+      for (int k = 0; k < n && !rc; k++) {
+        W.begin_tile();
+        if (!W.room(lens[(size_t)k])) rc = GSKYHIP_E_ARG;
+        W.end_tile();
+      }
+      st[0] += n;
+    }
+    st[1] += (int64_t)sp.width * sp.height * sp.ts;
   }
-  put_le<uint64_t>(o, 0);   // no next IFD
-  o.insert(o.end(), tail.begin(), tail.end());
-  for (int k = 0; k < 8; k++) o[8 + k] = (uint8_t)(ifd >> (8 * k));
-  if ((int64_t)o.size() > capacity) return GSKYHIP_E_ARG;
-  std::memcpy(out, o.data(), o.size());
-  *size = (int64_t)o.size();
-  return 0;
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  if (!rc) rc = W.finish(sp, size);
+  if (!rc && stats) std::memcpy(stats, st, sizeof(st));
+  return rc;
+}
+
+static int encode_geotiff_opts(const void *const *bands, int n_bands, int dtype, int width, int height,
+                               const double *geot, int epsg, const double *nodata, const char *const *names,
+                               int block_x, int block_y, int compression, int predictor, int zlevel, int deflate,
+                               int slab_tiles, int n_threads, uint8_t *out, int64_t capacity, int64_t *size,
+                               int64_t *stats, hipStream_t s) {
+  if (stats) std::memset(stats, 0, 4 * sizeof(int64_t));
+  if (!bands || !geot || !out || !size || n_bands <= 0 || n_bands > 4096) return GSKYHIP_E_ARG;
+  tiff::Spec sp;
+  sp.n_bands = n_bands; sp.dtype = dtype; sp.width = width; sp.height = height;
+  sp.geot = geot; sp.epsg = epsg; sp.nodata = nodata; sp.names = names;
+  sp.block_x = block_x; sp.block_y = block_y; sp.compression = compression; sp.predictor = predictor;
+  const int bad = sp.check();
+  if (bad) return bad;
+  if (zlevel < 0 || zlevel > 9 || (deflate != GSKYHIP_DEFLATE_HOST && deflate != GSKYHIP_DEFLATE_DEVICE) ||
+      slab_tiles < 0)
+    return GSKYHIP_E_ARG;
+  if (capacity < gskyhip_geotiff_bound_opts(width, height, n_bands, dtype, block_x, block_y, compression))
+    return GSKYHIP_E_ARG;
+  if (deflate == GSKYHIP_DEFLATE_HOST) {   // one copy of every band to the host, then the host writer
+    const size_t nb = (size_t)width * height * sp.ts;
+    std::vector<std::vector<uint8_t>> host((size_t)n_bands);
+    std::vector<const void *> ptrs((size_t)n_bands, nullptr);
+    for (int b = 0; b < n_bands; b++) {
+      if (!bands[b] || sp.empty[b]) continue;
+      host[b].resize(nb);
+      if (hipMemcpyAsync(host[b].data(), bands[b], nb, hipMemcpyDeviceToHost, s) != hipSuccess) return GSKYHIP_E_HIP;
+      ptrs[b] = host[b].data();
+    }
+    if (hipStreamSynchronize(s) != hipSuccess) return GSKYHIP_E_HIP;
+    return tiff::encode_host(sp, ptrs.data(), zlevel, n_threads, out, capacity, size);
+  }
+  if (compression == GSKYHIP_TIFF_PACKBITS) {   // the unchanged writer, on a workspace of this call's
+    const int64_t ws_bytes = gskyhip_geotiff_workspace_size(width, height, n_bands, dtype, block_x, block_y);
+    void *ws = nullptr;
+    if (hipMalloc(&ws, (size_t)ws_bytes) != hipSuccess) return GSKYHIP_E_HIP;
+    const int rc = gskyhip_encode_geotiff(bands, n_bands, dtype, width, height, geot, epsg, nodata, names, block_x,
+                                          block_y, ws, ws_bytes, out, capacity, size, s);
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(ws);
+    if (!rc && stats) stats[3] = ws_bytes;
+    return rc;
+  }
+  return encode_geotiff_device(sp, bands, zlevel, slab_tiles, out, capacity, size, stats, s);
+}
+
+int gskyhip_encode_geotiff_opts(const void *const *bands, int n_bands, int dtype, int width, int height,
+                                const double *geot, int epsg, const double *nodata, const char *const *names,
+                                int block_x, int block_y, int compression, int predictor, int zlevel, int deflate,
+                                int slab_tiles, int n_threads, uint8_t *out, int64_t capacity, int64_t *size,
+                                int64_t *stats, void *stream) {
+  try {
+    return encode_geotiff_opts(bands, n_bands, dtype, width, height, geot, epsg, nodata, names, block_x, block_y,
+                               compression, predictor, zlevel, deflate, slab_tiles, n_threads, out, capacity, size,
+                               stats, (hipStream_t)stream);
+  } catch (...) {
+    return GSKYHIP_E_HIP;
+  }
 }
 
 }  // extern "C"

@@ -41,13 +41,44 @@ def encode_png(rgba: torch.Tensor, sizes: Optional[Sequence[Tuple[int, int]]] = 
 _TIFF_DTYPES = {torch.uint8: 1, torch.int8: 100, torch.int16: 3, torch.float32: 6}
 
 
+DEFLATE_HOST, DEFLATE_DEVICE = 0, 1
+TIFF_PACKBITS, TIFF_DEFLATE = 32773, 8
+
+
+def _tiff_options(who, compression, predictor, zlevel, deflate, slab_tiles):
+    """The checked (compression code, predictor, zlevel, deflate code, slab_tiles)."""
+    if compression not in ("packbits", "deflate"):
+        raise ValueError('%s: compression must be "packbits" or "deflate", not %r' % (who, compression))
+    if deflate not in ("host", "device"):
+        raise ValueError('%s: deflate must be "host" or "device", not %r' % (who, deflate))
+    if predictor not in (1, 2, 3) or (compression == "packbits" and predictor != 1):
+        raise ValueError("%s: predictor must be 1, 2 or 3 (1 with packbits), not %r" % (who, predictor))
+    if not 0 <= int(zlevel) <= 9 or int(slab_tiles) < 0:
+        raise ValueError("%s: zlevel must be 0..9 and slab_tiles >= 0" % who)
+    return (TIFF_DEFLATE if compression == "deflate" else TIFF_PACKBITS, int(predictor), int(zlevel),
+            DEFLATE_DEVICE if deflate == "device" else DEFLATE_HOST, int(slab_tiles))
+
+
 def encode_geotiff(bands: Sequence[torch.Tensor], geot: Sequence[float], epsg: int,
                    nodata: Optional[Sequence[float]] = None, names: Optional[Sequence[str]] = None,
-                   block: Tuple[int, int] = (1024, 256), uint16: bool = False) -> bytes:
+                   block: Tuple[int, int] = (1024, 256), uint16: bool = False, compression: str = "packbits",
+                   predictor: int = 1, zlevel: int = 6, deflate: str = "device", slab_tiles: int = 0,
+                   return_stats: bool = False, threads: int = 16):
     """GeoTIFF bytes of a coverage: `bands` (height, width) device tensors of
     one dtype (uint8, int8, int16 -- uint16 when `uint16`, the bits held in
     int16 --, float32), what EncodeGdal writes for format "geotiff" with
-    the block size ows.go passes (1024 x 256)."""
+    the block size ows.go passes (1024 x 256): COMPRESS=PACKBITS.
+    compression="deflate" (beyond the reference, which always writes PackBits)
+    makes every tile one zlib stream after TIFF predictor `predictor` (1 none,
+    2 horizontal differencing, 3 floating point: float32 only), by this
+    library's Deflate encoder at `zlevel` (0 stored, 1-9 the one encoding).
+    deflate="device": the tiles are gathered, predicted and deflated in HBM in
+    slabs of `slab_tiles` tiles (0: the library's choice) and only compressed
+    bytes are copied; deflate="host": the bands are copied to the host and
+    `threads` host threads run the same encoder -- the same file.
+    return_stats: also the tuple (tiles deflated on the device, raw bytes read
+    from HBM, compressed bytes copied to the host, device workspace bytes)."""
+    comp, pred, zl, mode, slab = _tiff_options("encode_geotiff", compression, predictor, zlevel, deflate, slab_tiles)
     if not bands:
         raise ValueError("encode_geotiff: no bands")
     dt = bands[0].dtype
@@ -59,26 +90,90 @@ def encode_geotiff(bands: Sequence[torch.Tensor], geot: Sequence[float], epsg: i
     n = len(bands)
     L = lib()
     bx, by = int(block[0]), int(block[1])
-    ws = torch.empty(max(1, int(L.gskyhip_geotiff_workspace_size(w, h, n, code, bx, by))), dtype=torch.uint8,
-                     device=bands[0].device)
-    cap = int(L.gskyhip_geotiff_bound(w, h, n, code, bx, by))
-    if cap <= 0:
-        raise ValueError("encode_geotiff: bad size / block")
-    out = np.empty(cap, np.uint8)
-    size = C.c_int64(0)
     ptrs = (C.c_void_p * n)(*[b.data_ptr() for b in bands])   # EmptyTile bands: skipped by the writer
     gt = (C.c_double * 6)(*[float(v) for v in geot])
     nd = np.asarray(nodata, np.float64) if nodata is not None else None
     nm = (C.c_char_p * n)(*[s.encode() for s in names]) if names is not None else None
-    check(L.gskyhip_encode_geotiff(ptrs, n, code, w, h, gt, int(epsg),
-                                   nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm, bx, by,
-                                   C.c_void_p(ws.data_ptr()), ws.numel(), out.ctypes.data_as(C.c_void_p), cap,
-                                   C.byref(size), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
-          "encode_geotiff")
+    size = C.c_int64(0)
+    if comp == TIFF_PACKBITS and not return_stats:
+        ws = torch.empty(max(1, int(L.gskyhip_geotiff_workspace_size(w, h, n, code, bx, by))), dtype=torch.uint8,
+                         device=bands[0].device)
+        cap = int(L.gskyhip_geotiff_bound(w, h, n, code, bx, by))
+        if cap <= 0:
+            raise ValueError("encode_geotiff: bad size / block")
+        out = np.empty(cap, np.uint8)
+        check(L.gskyhip_encode_geotiff(ptrs, n, code, w, h, gt, int(epsg),
+                                       nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm, bx, by,
+                                       C.c_void_p(ws.data_ptr()), ws.numel(), out.ctypes.data_as(C.c_void_p), cap,
+                                       C.byref(size), C.c_void_p(torch.cuda.current_stream().cuda_stream)),
+              "encode_geotiff")
+        return out[:size.value].tobytes()
+    cap = int(L.gskyhip_geotiff_bound_opts(w, h, n, code, bx, by, comp))
+    if cap <= 0:
+        raise ValueError("encode_geotiff: bad size / block")
+    out = np.empty(cap, np.uint8)
+    stats = (C.c_int64 * 4)()
+    with torch.cuda.device(bands[0].device):
+        check(L.gskyhip_encode_geotiff_opts(ptrs, n, code, w, h, gt, int(epsg),
+                                            nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm, bx, by,
+                                            comp, pred, zl, mode, slab, int(threads),
+                                            out.ctypes.data_as(C.c_void_p), cap, C.byref(size), stats,
+                                            C.c_void_p(torch.cuda.current_stream(bands[0].device).cuda_stream)),
+              "encode_geotiff_opts")
+    data = out[:size.value].tobytes()
+    return (data, tuple(stats)) if return_stats else data
+
+
+_HOST_CODES = {np.dtype(np.uint8): 1, np.dtype(np.int8): 100, np.dtype(np.int16): 3, np.dtype(np.float32): 6,
+               np.dtype(np.uint16): 2}
+
+
+def geotiff_bound(width: int, height: int, n_bands: int, dtype, block: Tuple[int, int] = (1024, 256),
+                  compression: str = "packbits") -> int:
+    """gskyhip_geotiff_bound_opts: the most bytes encode_geotiff[_host] writes (0: bad arguments)."""
+    if compression not in ("packbits", "deflate"):
+        raise ValueError('geotiff_bound: compression must be "packbits" or "deflate", not %r' % (compression,))
+    return int(lib().gskyhip_geotiff_bound_opts(int(width), int(height), int(n_bands), _HOST_CODES[np.dtype(dtype)],
+                                                int(block[0]), int(block[1]),
+                                                TIFF_DEFLATE if compression == "deflate" else TIFF_PACKBITS))
+
+
+def encode_geotiff_host(bands: Sequence[np.ndarray], geot: Sequence[float], epsg: int,
+                        nodata: Optional[Sequence[float]] = None, names: Optional[Sequence[str]] = None,
+                        block: Tuple[int, int] = (1024, 256), compression: str = "packbits", predictor: int = 1,
+                        zlevel: int = 6, threads: int = 4) -> bytes:
+    """encode_geotiff of host numpy bands (gskyhip_encode_geotiff_host; no
+    device, no HIP call): the file encode_geotiff writes for the same samples
+    and options, byte for byte.  A band may be None when its name starts with
+    "EmptyTile" (it is skipped, as EncodeGdal skips it)."""
+    comp, pred, zl, _, _ = _tiff_options("encode_geotiff_host", compression, predictor, zlevel, "host", 0)
+    real = [b for b in bands if b is not None] if bands else []
+    if not real:
+        raise ValueError("encode_geotiff_host: no bands")
+    dt = np.dtype(real[0].dtype)
+    if dt not in _HOST_CODES or any(b.dtype != dt or b.shape != real[0].shape or b.ndim != 2 for b in real):
+        raise ValueError("encode_geotiff_host: bands must be 2-D arrays of one shape and a GeoTIFF dtype")
+    code = _HOST_CODES[dt]
+    h, w = int(real[0].shape[0]), int(real[0].shape[1])
+    bands = [np.ascontiguousarray(b) if b is not None else None for b in bands]
+    n = len(bands)
+    L = lib()
+    bx, by = int(block[0]), int(block[1])
+    cap = int(L.gskyhip_geotiff_bound_opts(w, h, n, code, bx, by, comp))
+    if cap <= 0:
+        raise ValueError("encode_geotiff_host: bad size / block")
+    out = np.empty(cap, np.uint8)
+    size = C.c_int64(0)
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data if b is not None else None for b in bands])
+    gt = (C.c_double * 6)(*[float(v) for v in geot])
+    nd = np.asarray(nodata, np.float64) if nodata is not None else None
+    nm = (C.c_char_p * n)(*[s.encode() for s in names]) if names is not None else None
+    check(L.gskyhip_encode_geotiff_host(ptrs, n, code, w, h, gt, int(epsg),
+                                        nd.ctypes.data_as(C.c_void_p) if nd is not None else None, nm, bx, by, comp,
+                                        pred, zl, int(threads), out.ctypes.data_as(C.c_void_p), cap, C.byref(size)),
+          "encode_geotiff_host")
     return out[:size.value].tobytes()
 
-
-DEFLATE_HOST, DEFLATE_DEVICE = 0, 1
 
 
 def encode_netcdf(bands: Sequence[torch.Tensor], geot: Sequence[float], epsg: int,

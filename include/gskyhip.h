@@ -845,6 +845,63 @@ int gskyhip_encode_geotiff(const void *const *bands, int n_bands, int dtype, int
                            const double *geot, int epsg, const double *nodata, const char *const *names,
                            int block_x, int block_y, void *workspace, int64_t workspace_bytes, uint8_t *out,
                            int64_t capacity, int64_t *size, void *stream);
+/* gskyhip_encode_geotiff with a choice of compression, beyond the reference
+ * (EncodeGdalOpen always writes COMPRESS=PACKBITS, which removes nothing from
+ * int16 reflectances or float32 fields).
+ * compression = GSKYHIP_TIFF_PACKBITS (predictor must be 1): the file of
+ * gskyhip_encode_geotiff, byte for byte.
+ * compression = GSKYHIP_TIFF_DEFLATE: tag 259 = 8 (Adobe Deflate); every tile
+ * is one complete zlib stream of its block_y x block_x samples (edge tiles
+ * padded as the PackBits writer pads them) after the TIFF predictor, tag 317,
+ * written only when it is not 1:
+ *   1  none;
+ *   2  horizontal differencing, any dtype: the differences of the samples' bit
+ *      patterns along a tile row, wrapping in the sample width, the first
+ *      sample of each tile row kept (float32: of the 32-bit patterns);
+ *   3  floating point (TIFF Technical Note 3), GSKYHIP_FLOAT32 only: per tile
+ *      row the four byte planes, most significant first, then byte differences
+ *      one apart over the row of 4 * block_x bytes.
+ * Every other tag, the layout and the EmptyTile rules are those of
+ * gskyhip_encode_geotiff.  The streams are this library's encoder's
+ * (gskyhip_deflate_blocks; zlevel 0: stored blocks, 1-9: the one encoding),
+ * neither zlib's nor GDAL's bytes: parity is on decoded content, and
+ * gskyhip_geotiff_read[_decode] reads the file back.
+ * deflate = GSKYHIP_DEFLATE_DEVICE: per band and slab of slab_tiles tiles
+ * (0: the library's choice, 16 MiB of raw tile bytes, at least one tile,
+ * at most 32768) a kernel gathers the tiles from the band in HBM and applies
+ * the predictor, gskyhip_deflate_blocks' kernels turn each tile into its
+ * stream, the streams are packed on the device, and the host receives the
+ * lengths and statuses and then one copy of exactly the compressed bytes,
+ * straight to their place in `out`.  The device workspace (about 8.4 times the
+ * slab's raw bytes) is allocated inside the call and freed before return.  The
+ * file does not depend on slab_tiles.  A band without samples (EmptyTile, or a
+ * NULL pointer) is one tile compressed once on the host and repeated.
+ * deflate = GSKYHIP_DEFLATE_HOST: the bands are copied to the host once and
+ * the same predictor and encoder run on up to n_threads host threads: the same
+ * file, byte for byte.
+ * stats (HOST int64[4], or NULL) = {tiles deflated on the device, raw bytes
+ * read from HBM, compressed bytes copied to the host, device workspace bytes};
+ * all zero in the host mode and after a failed call.
+ * GSKYHIP_E_ARG / GSKYHIP_E_TYPE, before any device work, for what
+ * gskyhip_encode_geotiff refuses and for an unknown compression, a predictor
+ * outside 1-3 (or 3 on another type than float32, or not 1 with PackBits),
+ * zlevel outside 0-9, deflate outside {0, 1}, slab_tiles < 0, a tile above
+ * 1 GiB, or capacity < gskyhip_geotiff_bound_opts.  A tile whose stream fails
+ * fails the call. */
+#define GSKYHIP_TIFF_PACKBITS 32773
+#define GSKYHIP_TIFF_DEFLATE 8
+int64_t gskyhip_geotiff_bound_opts(int width, int height, int n_bands, int dtype, int block_x, int block_y,
+                                   int compression);
+int gskyhip_encode_geotiff_opts(const void *const *bands, int n_bands, int dtype, int width, int height,
+                                const double *geot, int epsg, const double *nodata, const char *const *names,
+                                int block_x, int block_y, int compression, int predictor, int zlevel, int deflate,
+                                int slab_tiles, int n_threads, uint8_t *out, int64_t capacity, int64_t *size,
+                                int64_t *stats, void *stream);
+/* The same file from HOST band pointers: no device involved, no HIP call. */
+int gskyhip_encode_geotiff_host(const void *const *bands, int n_bands, int dtype, int width, int height,
+                                const double *geot, int epsg, const double *nodata, const char *const *names,
+                                int block_x, int block_y, int compression, int predictor, int zlevel, int n_threads,
+                                uint8_t *out, int64_t capacity, int64_t *size);
 
 /* EncodeGdalOpen + EncodeGdal for format "netcdf" (utils/ogc_encoders.go:
  * 263-301, creation options COMPRESS=DEFLATE, ZLEVEL=6; ows.go:1172) of one
