@@ -16,7 +16,10 @@
 // restates; parity with the govaluate fork itself is unpinned.
 // Grammar: ?: (right assoc.), ||, &&, == !=, < <= > >=, + -, * / %, ** (right
 // assoc.), unary - ! +, numbers, variables, parentheses; comparisons and
-// logic yield 1.0 / 0.0.
+// logic yield 1.0 / 0.0.  ?: is eager (condition, both arms, select).  The
+// limits -- kMaxStack slots, kMaxCode words -- and what they mean for nesting,
+// chains and chained ternaries are spelt out in include/gskyhip.h and pinned
+// by tests/test_band_math_edges.py.
 #include <hip/hip_runtime.h>
 
 #include <cctype>
@@ -160,9 +163,17 @@ struct Parser {
       return;
     }
     if (std::isdigit((unsigned char)*s) || (*s == '.' && std::isdigit((unsigned char)s[1]))) {
-      char *end = nullptr;
-      const double v = std::strtod(s, &end);
-      s = end;
+      // digits [. digits] | . digits, then e|E [+|-] digits: only that much
+      // goes to strtod, which on its own also reads hex ("0x10", "0x1p3")
+      const char *b = s;
+      while (std::isdigit((unsigned char)*s)) s++;
+      if (*s == '.') { s++; while (std::isdigit((unsigned char)*s)) s++; }
+      if (*s == 'e' || *s == 'E') {
+        const char *e = s + 1;
+        if (*e == '+' || *e == '-') e++;
+        if (std::isdigit((unsigned char)*e)) { while (std::isdigit((unsigned char)*e)) e++; s = e; }
+      }
+      const double v = std::strtod(std::string(b, s).c_str(), nullptr);
       emit(OP_CONST, (float)v, 1);
       return;
     }
@@ -274,7 +285,7 @@ extern "C" int gskyhip_band_math(const char *expr, const char *const *var_names,
   vars.n = n_vars;
   bool any = false;
   for (int k = 0; k < n_vars; k++) {
-    if (!canvases || !dtypes || !nodatas || !canvases[k]) return GSKYHIP_E_ARG;
+    if (!canvases || !dtypes || !nodatas || (n_px > 0 && !canvases[k])) return GSKYHIP_E_ARG;
     switch (dtypes[k]) {
       case GSKYHIP_BYTE: case GSKYHIP_SIGNEDBYTE: case GSKYHIP_INT16: case GSKYHIP_UINT16: case GSKYHIP_FLOAT32:
         break;

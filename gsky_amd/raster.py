@@ -241,7 +241,9 @@ def band_math(expr: str, variables: Sequence[tuple], out_nodata: float) -> torch
     (typed canvases of the merged namespaces, all the same shape), result a
     float32 tensor of that shape.  Pixels where any variable is its nodata,
     and non-finite results, are `out_nodata` (the first namespace's nodata).
-    Raises GskyError(-1) on a parse error or unknown variable."""
+    Raises GskyError(-1) on a parse error, an unknown variable, or an
+    expression above the limits of include/gskyhip.h (16 stack slots, 96
+    program words: 7 conditions in a chained ?:)."""
     if not variables:
         raise ValueError("band_math needs the axis variables")
     if len(variables) > 8:

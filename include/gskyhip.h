@@ -656,8 +656,32 @@ int gskyhip_service_shutdown(const char *socket_path);
  * of dtypes[k], nodata nodatas[k]) -- into out (dev float32 n_px).  A pixel
  * where any variable equals its nodata, or whose result is not finite,
  * becomes out_nodata (the first namespace's nodata); an expression without
- * variables fills every valid pixel.  GSKYHIP_E_ARG: parse error / unknown
- * variable (govaluate's errors); GSKYHIP_E_TYPE: canvas type. */
+ * variables fills every valid pixel with its value unfiltered, finite or not
+ * ("1e39" writes inf, "0 / 0" NaN), as the reference does with a scalar
+ * result (tile_merger.go:698-708).  Every variable of the axis masks,
+ * referenced or not; the comparison is float64(float32(v)) == nodata, so a
+ * NaN nodata, or one that is no float32 value, masks nothing.
+ * Grammar, loosest first: ?: (right-associative), ||, &&, == !=, < <= > >=,
+ * + -, * / %, ** (right-associative), unary - ! +; all other binary
+ * operators associate to the left.  == and != bind looser than the four
+ * relations: "a == b < c" is a == (b < c).  Unary operators bind tighter
+ * than **: "-a ** 2" is (-a) ** 2, and "2 ** -1" is 0.5.  Comparisons, !, &&
+ * and || yield 1.0 / 0.0; everything but 0.0 and -0.0 is true, NaN included.
+ * % is C fmod (sign of the dividend).  Numbers are decimal: digits [. digits]
+ * or . digits, then an optional e|E [+|-] digits, rounded to float32; hex
+ * forms, "inf" and "nan" are not numbers.  Names are [A-Za-z_][A-Za-z0-9_.]*,
+ * case-sensitive.
+ * ?: evaluates the condition and both arms, then selects.  An expression may
+ * need at most 16 stack slots (operands pending at once) and compile to at
+ * most 96 program words (one per number, variable reference and operator;
+ * parentheses and unary + cost none).  So "a+(a+(..." nests 16 operands deep,
+ * a chain "a+a+...+a" holds 48 terms, and since each pending arm of a chained
+ * ternary keeps two slots, "c1 ? v1 : c2 ? v2 : ... : last" holds 7
+ * conditions at most.
+ * GSKYHIP_E_ARG: parse error, unknown variable (govaluate's errors), an
+ * expression above either limit, n_vars outside 0..8 or a NULL pointer (the
+ * canvases and out may be NULL when n_px is 0); out is then untouched.
+ * GSKYHIP_E_TYPE: canvas type. */
 #define GSKYHIP_BANDMATH_MAX_VARS 8
 int gskyhip_band_math(const char *expr, const char *const *var_names, const void *const *canvases,
                       const int32_t *dtypes, const double *nodatas, int n_vars, int64_t n_px, double out_nodata,
