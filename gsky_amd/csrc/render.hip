@@ -832,15 +832,105 @@ __device__ void plan_pair(const PlanArgs &a, int p, double *sx, double *sy, int 
   pp.stamp = g.timestamp + (double)g.polygon_hash;
 }
 
+// ---------------------------------------------------------------- pair-less tiles
+// Tiles with pair_begin == pair_end come out of the band kernel transparent:
+// plan_tiles leaves created[] 0, so its palette table is all zero and it
+// stores 0 to rows < height, columns < width of the tile's max_h x max_w RGBA
+// slot (a tile outside the slot is complex and written by no kernel).  Those
+// stores depend on nothing the planners compute, and the planners leave most
+// of the HBM write bandwidth idle, so for an eligible call (launch_render) a
+// few extra workgroups at the low block indices of plan_pairs_kernel and
+// plan_rows_kernel issue them there, each launch its share of every tile's
+// rows, and the band kernel returns for those tiles (RenderArgs.skip_pairless).
+struct FillArgs {
+  uint8_t *rgba;     // the call's RGBA output; NULL: the launch carries no fill groups
+  int n_groups;      // fill workgroups in front of the planner's own
+  int waves;         // waves of a fill group that write (the others end at once and free their slots)
+  int lo16, hi16;    // the launch's rows of a tile: [height * lo16 / 16, height * hi16 / 16)
+  int slices;        // workers that share one tile's rows
+};
+
+// One wave = one worker out of n_workers.  Worker (i, j), i = worker / R,
+// j = worker % R: slice j of R of the launch's rows in every pair-less tile
+// of tile set i of S, where R = min(slices, n_workers) and S = n_workers / R.
+// Of the S consecutive tiles q S .. q S + S - 1 each set holds one, rotated
+// by a hash of q: pair-less tiles come in runs and in columns of the request
+// grid (the rim of the coverage), and a plain t % S puts a whole grid column
+// into one set whenever S divides the grid's width.  The emptiness test reads
+// the tile array here, 64 tiles per round of loads.  Out of line: the
+// carrier kernels keep their registers.
+__device__ __noinline__ void fill_pairless(const gskyhip_tile *tiles, int n_tiles, int max_h, int max_w,
+                                           uint8_t *rgba, int worker, int n_workers, int lo16, int hi16,
+                                           int slices) {
+  const int lane = threadIdx.x & 63;
+  const int R = max(1, min(slices, n_workers)), S = n_workers / R;
+  const int i = worker / R, j = worker - i * R;
+  if (i >= S) return;
+  // tile of set i among tiles q S ..: q S + (i + hash(q)) % S
+  auto set_tile = [&](int q) {
+    const uint32_t h = ((uint32_t)q * 0x9E3779B1u) >> 16;
+    return (int64_t)S * q + (int)(((uint32_t)i + h) % (uint32_t)S);
+  };
+  // 16-byte stores need every row of every slot on a 16-byte address
+  const bool vec = (max_w & 3) == 0 && ((uintptr_t)rgba & 15) == 0;
+  const u32x4 z4 = {0u, 0u, 0u, 0u};
+  for (int k0 = 0; (int64_t)S * k0 < n_tiles; k0 += 64) {
+    const int64_t tl = set_tile(k0 + lane);
+    int W = 0, H = 0;
+    bool empty = false;
+    if (tl < n_tiles) {
+      const gskyhip_tile &q = tiles[tl];
+      W = q.width; H = q.height;
+      empty = q.pair_begin == q.pair_end && W > 0 && H > 0 && W <= max_w && H <= max_h;
+    }
+    unsigned long long m = __ballot(empty);
+    while (m) {
+      const int l = __builtin_ctzll(m);
+      m &= m - 1;
+      const int w = __shfl(W, l, 64), h = __shfl(H, l, 64);
+      const int64_t t = set_tile(k0 + l);
+      const int ra = (int)((int64_t)h * lo16 / 16), rb = (int)((int64_t)h * hi16 / 16);
+      const int r0 = ra + (int)((int64_t)(rb - ra) * j / R), r1 = ra + (int)((int64_t)(rb - ra) * (j + 1) / R);
+      if (r1 <= r0) continue;
+      uint32_t *dst = (uint32_t *)rgba + (t * max_h + r0) * (int64_t)max_w;
+      if (vec && w == max_w) {   // the rows are one contiguous run
+        const int64_t n4 = (int64_t)(r1 - r0) * (w >> 2);
+        for (int64_t c = lane; c < n4; c += 64) __builtin_nontemporal_store(z4, (GPTR(u32x4))((u32x4 *)dst + c));
+      } else {
+        const int n4 = vec ? w >> 2 : 0;
+        for (int r = r0; r < r1; r++, dst += max_w) {
+          for (int c = lane; c < n4; c += 64) __builtin_nontemporal_store(z4, (GPTR(u32x4))((u32x4 *)dst + c));
+          for (int c = 4 * n4 + lane; c < w; c += 64) __builtin_nontemporal_store(0u, (GPTR(uint32_t))(dst + c));
+        }
+      }
+    }
+  }
+}
+
+// The fill role of a carrier kernel's workgroup `group` (< f.n_groups).
+__device__ __forceinline__ void fill_group(const PlanArgs &a, const FillArgs &f, int group) {
+  const int wave = threadIdx.x >> 6, waves = min(f.waves, (int)(blockDim.x >> 6));
+  if (wave >= waves) return;
+  fill_pairless(a.tiles, a.n_tiles, a.max_h, a.max_w, f.rgba, group * waves + wave, f.n_groups * waves, f.lo16,
+                f.hi16, f.slices);
+}
+
 // One workgroup of NT threads per pair: NT = 64 (one wavefront) for batches
-// that fill the GPU, NT = 256 for small, latency-bound batches.
+// that fill the GPU, NT = 256 for small, latency-bound batches.  The first
+// f.n_groups workgroups write pair-less tiles instead (resident from the
+// start of the launch; the pairs' workgroups follow them).
 template <int NT>
-__global__ __launch_bounds__(NT) void plan_pairs_kernel(PlanArgs a) {
-  if ((int)blockIdx.x >= a.n_pairs) return;
+__global__ __launch_bounds__(NT) void plan_pairs_kernel(PlanArgs a, FillArgs f) {
+  int p = blockIdx.x;
+  if (f.n_groups > 0) {
+    if (p < f.n_groups) { fill_group(a, f, p); return; }
+    p -= f.n_groups;
+  }
+  if (p >= a.n_pairs) return;
   __shared__ double sx[kGrid], sy[kGrid];
   __shared__ int sok[kGrid];
   __shared__ Xform ts;
-  plan_pair<NT>(a, blockIdx.x, sx, sy, sok, ts);
+  plan_pair<NT>(a, p, sx, sy, sok, ts);
 }
 
 // ---------------------------------------------------------------- extent op
@@ -1355,9 +1445,18 @@ __device__ __forceinline__ void plan_row(const PlanArgs &a, int p, const PairPla
 
 // Workgroups of one pair (blockIdx.x: pair, blockIdx.y: 256-row chunk): the
 // pair's plan and transformer are wave-uniform, so their fields arrive
-// through scalar loads rather than per-lane gathers.
-__global__ __launch_bounds__(256) void plan_rows_kernel(PlanArgs a) {
-  const int p = blockIdx.x;
+// through scalar loads rather than per-lane gathers.  Workgroups
+// (x < f.n_groups, y = 0), the first the launch dispatches, write pair-less
+// tiles instead (fill_pairless); the pairs follow at x - f.n_groups.
+__global__ __launch_bounds__(256) void plan_rows_kernel(PlanArgs a, FillArgs f) {
+  int p = blockIdx.x;
+  if (f.n_groups > 0) {
+    if (p < f.n_groups) {
+      if (blockIdx.y == 0) fill_group(a, f, p);
+      return;
+    }
+    p -= f.n_groups;
+  }
   const int row = blockIdx.y * blockDim.x + threadIdx.x;
   if (p >= a.n_pairs) return;
   const PairPlan &pp = a.pairs[p];
@@ -2045,7 +2144,18 @@ int64_t render_workspace_size(int n_tiles, int n_pairs, int max_h) {
   return carve(nullptr, n_tiles, n_pairs, max_h).total;
 }
 
-static int plan_all(const RenderCall &rc, Carve &cv) {
+// Fill-role shape of the two carrier launches (measured on
+// C2): workgroups per launch, writing waves of a plan_rows fill group, and
+// the 16ths of each tile's rows that plan_pairs_kernel's groups take (the
+// rest go to plan_rows_kernel's).
+constexpr int kFillGroupsPairs = 256, kFillGroupsRows = 256, kFillWavesRows = 1, kFillSplit16 = 8;
+constexpr int kFillRowSlices = 16;
+
+// fill_rgba: the RGBA output of a call whose pair-less tiles the planner
+// launches may write (launch_render's eligibility test), else NULL.  *filled
+// = true exactly when both fill-carrying launches were issued.
+static int plan_all(const RenderCall &rc, Carve &cv, uint8_t *fill_rgba = nullptr, bool *filled = nullptr) {
+  if (filled) *filled = false;
   if (rc.n_tiles <= 0) return 0;
   if (!rc.workspace || rc.workspace_bytes < render_workspace_size(rc.n_tiles, rc.n_pairs, rc.max_h))
     return GSKYHIP_E_ARG;
@@ -2083,7 +2193,7 @@ static int plan_all(const RenderCall &rc, Carve &cv) {
 #endif
   a.small = small ? (rc.n_pairs <= kFusedPlanPairs ? 2 : 1) : 0;
   if (small) {
-    if (a.small == 1) hipLaunchKernelGGL(plan_pairs_kernel<256>, dim3(rc.n_pairs), dim3(256), 0, s, a);
+    if (a.small == 1) hipLaunchKernelGGL(plan_pairs_kernel<256>, dim3(rc.n_pairs), dim3(256), 0, s, a, FillArgs{});
     hipLaunchKernelGGL(plan_small_kernel, dim3(1), dim3(256), 0, s, a);
 #ifdef GSKYHIP_AB
     if (getenv("GSKYHIP_PLAN_STAMPS")) {   // phase times of plan_small_kernel, 10 ns ticks
@@ -2113,10 +2223,29 @@ static int plan_all(const RenderCall &rc, Carve &cv) {
 #ifdef GSKYHIP_AB
   if (const char *sp = getenv("GSKYHIP_PAIRS_SMALL")) small_pairs = atoi(sp);
 #endif
+  // pair-less tiles: fill groups in front of the pairs' and the rows'
+  // workgroups (both launches are issued whenever the batch has a pair)
+  FillArgs fp{}, fr{};
+  if (fill_rgba && rc.n_pairs > 0) {
+    int gp = kFillGroupsPairs, gr = kFillGroupsRows, wr = kFillWavesRows, split = kFillSplit16;
+    int slices = kFillRowSlices;
+#ifdef GSKYHIP_AB
+    if (const char *e = getenv("GSKYHIP_FILL_GROUPS_PAIRS")) gp = std::max(1, atoi(e));
+    if (const char *e = getenv("GSKYHIP_FILL_GROUPS_ROWS")) gr = std::max(1, atoi(e));
+    if (const char *e = getenv("GSKYHIP_FILL_WAVES_ROWS")) wr = std::min(4, std::max(1, atoi(e)));
+    if (const char *e = getenv("GSKYHIP_FILL_SPLIT")) split = std::min(16, std::max(0, atoi(e)));
+    if (const char *e = getenv("GSKYHIP_FILL_SLICES")) slices = std::max(1, atoi(e));
+#endif
+    fp.rgba = fr.rgba = fill_rgba;
+    fp.slices = fr.slices = slices;
+    fp.n_groups = gp; fp.waves = 1; fp.lo16 = 0; fp.hi16 = split;
+    fr.n_groups = gr; fr.waves = wr; fr.lo16 = split; fr.hi16 = 16;
+    if (filled) *filled = true;
+  }
   if (rc.n_pairs > 0 && rc.n_pairs <= small_pairs)
-    hipLaunchKernelGGL(plan_pairs_kernel<256>, dim3(rc.n_pairs), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(plan_pairs_kernel<256>, dim3(rc.n_pairs + fp.n_groups), dim3(256), 0, s, a, fp);
   else if (rc.n_pairs > 0)
-    hipLaunchKernelGGL(plan_pairs_kernel<64>, dim3(rc.n_pairs), dim3(64), 0, s, a);
+    hipLaunchKernelGGL(plan_pairs_kernel<64>, dim3(rc.n_pairs + fp.n_groups), dim3(64), 0, s, a, fp);
   if (rc.n_pairs >= kTiles4MinPairsPerTile * rc.n_tiles)
     hipLaunchKernelGGL(plan_tiles4_kernel, dim3(rc.n_tiles), dim3(256), 0, s, a);
   else
@@ -2125,7 +2254,8 @@ static int plan_all(const RenderCall &rc, Carve &cv) {
     if (a.sep)
       hipLaunchKernelGGL(plan_cols_kernel, dim3((unsigned)((3 * (int64_t)rc.n_pairs + 255) / 256)), dim3(256), 0, s,
                          a);
-    hipLaunchKernelGGL(plan_rows_kernel, dim3(rc.n_pairs, (rc.max_h + 255) / 256), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(plan_rows_kernel, dim3(rc.n_pairs + fr.n_groups, (rc.max_h + 255) / 256), dim3(256), 0, s, a,
+                       fr);
     hipLaunchKernelGGL(plan_split_kernel, dim3(1024), dim3(64), 0, s, a);
     hipLaunchKernelGGL(plan_exact_kernel, dim3(512), dim3(256), 0, s, a);
   }
@@ -2154,9 +2284,43 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
   const bool autom = rgba_out && sp.offset == 0.0 && sp.scale == 0.0 && sp.clip == 0.0;
   if ((autom || !rgba_out) && !canvas_out) return GSKYHIP_E_ARG;
   if (rc.n_tiles <= 0) return 0;
+  // One value type, one namespace, no auto-scale: the typed band kernel, for
+  // RGBA output (GetMap) or typed canvases only (GetCoverage); complex tiles
+  // (exact transforms, type promotion) still go to render_general_kernel.
+  const int vt = single_value_type(rc.value_types);
+  const bool mask = rc.mask_ns >= 0;
+  const bool bil = rc.resample == GSKYHIP_RESAMPLE_BILINEAR;
+  int lds_mode = -1;
+  if (rc.resample == GSKYHIP_RESAMPLE_CUBIC) {
+    // cubic: float32 canvases without a mask layer have a band kernel
+    // (render_cub_kernel); every other combination runs the generic kernels
+    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask) lds_mode = kCanvas | kCubic;
+  } else if (rc.resample == GSKYHIP_RESAMPLE_AVERAGE) {
+    // average: the same combination has render_avg_kernel (render_area.h)
+    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask) lds_mode = kCanvas | kAverage;
+  } else if (rc.resample == GSKYHIP_RESAMPLE_MODE) {
+    // mode: the generic kernels
+  } else if (is_kernel(rc.resample)) {
+    // spline, Lanczos: the same combination has render_kern_kernel (render_kern.h)
+    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask)
+      lds_mode = kCanvas | (rc.resample == GSKYHIP_RESAMPLE_LANCZOS ? kLanczos : kSpline);
+  } else if (vt && n_out == 1 && !autom) {
+    if (rgba_out && !canvas_out) lds_mode = bil ? kBilinear : 0;
+    else if (!rgba_out && canvas_out) lds_mode = kCanvas | (bil ? kBilinear : 0);
+  }
+  // Pair-less tiles from the planner launches (fill_pairless): a whole call
+  // (phase 0) of the nearest-neighbour RGBA band kernel without a mask layer
+  // -- lds_mode 0 is RGBA out, no canvas, no auto-scale, one namespace -- that
+  // has a pair (else neither carrier kernel runs).  Phase 1 never touches the
+  // output and phase 2 alone writes every tile, as every other call does.
+  bool fill = phase == 0 && lds_mode == 0 && !mask && rc.n_pairs > 0;
+#ifdef GSKYHIP_AB
+  if (const char *e = getenv("GSKYHIP_FILL")) fill = fill && atoi(e) != 0;
+#endif
+  bool filled = false;
   Carve cv;
   if (phase != 2) {  // 0: plan + render, 1: plan only, 2: render only (plan done)
-    int rcode = plan_all(rc, cv);
+    int rcode = plan_all(rc, cv, fill ? rgba_out : nullptr, &filled);
     if (rcode || phase == 1) return rcode;
   } else {
     if (!rc.workspace || rc.workspace_bytes < render_workspace_size(rc.n_tiles, rc.n_pairs, rc.max_h))
@@ -2182,39 +2346,16 @@ int launch_render(const RenderCall &rc, const int32_t *out_ns, int n_out, const 
   a.lds_mode = 0;
   a.cov_offsets = rc.cov_offsets;
   a.cov_stride = rc.cov_stride;
+  a.skip_pairless = filled ? 1 : 0;
   const int bands = (rc.max_h + a.rows_per_block - 1) / a.rows_per_block;
   const dim3 grid((unsigned)(rc.n_tiles * bands));
   hipStream_t s = rc.stream;
-  const bool mask = rc.mask_ns >= 0;
   if (autom) {
     hipLaunchKernelGGL(minmax_init_kernel, dim3((rc.n_tiles * 3 + 255) / 256), dim3(256), 0, s, cv.minmax,
                        rc.n_tiles * 3);
     a.write_rgba = 0;
   } else {
     a.write_rgba = rgba_out ? 1 : 0;
-  }
-  // One value type, one namespace, no auto-scale: the typed band kernel, for
-  // RGBA output (GetMap) or typed canvases only (GetCoverage); complex tiles
-  // (exact transforms, type promotion) still go to render_general_kernel.
-  const int vt = single_value_type(rc.value_types);
-  const bool bil = rc.resample == GSKYHIP_RESAMPLE_BILINEAR;
-  int lds_mode = -1;
-  if (rc.resample == GSKYHIP_RESAMPLE_CUBIC) {
-    // cubic: float32 canvases without a mask layer have a band kernel
-    // (render_cub_kernel); every other combination runs the generic kernels
-    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask) lds_mode = kCanvas | kCubic;
-  } else if (rc.resample == GSKYHIP_RESAMPLE_AVERAGE) {
-    // average: the same combination has render_avg_kernel (render_area.h)
-    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask) lds_mode = kCanvas | kAverage;
-  } else if (rc.resample == GSKYHIP_RESAMPLE_MODE) {
-    // mode: the generic kernels
-  } else if (is_kernel(rc.resample)) {
-    // spline, Lanczos: the same combination has render_kern_kernel (render_kern.h)
-    if (vt == GSKYHIP_FLOAT32 && n_out == 1 && !rgba_out && canvas_out && !mask)
-      lds_mode = kCanvas | (rc.resample == GSKYHIP_RESAMPLE_LANCZOS ? kLanczos : kSpline);
-  } else if (vt && n_out == 1 && !autom) {
-    if (a.write_rgba && !canvas_out) lds_mode = bil ? kBilinear : 0;
-    else if (!rgba_out && canvas_out) lds_mode = kCanvas | (bil ? kBilinear : 0);
   }
   if (lds_mode >= 0) {
     a.lds_mode = lds_mode;

@@ -210,6 +210,8 @@ struct RenderArgs {
   int lds_mode;          // typed band kernels: kBilinear | kCanvas | kCubic | kAverage | kSpline | kLanczos bits of the call
   const int64_t *cov_offsets;  // canvas mode: per tile element offset into one image (NULL: slots)
   int64_t cov_stride;          // ... and that image's row stride (elements)
+  int skip_pairless;           // 1: the planner launches of this call wrote the tiles with pair_begin == pair_end
+                               // (render.hip, fill_pairless); render_nn_kernel<.., MASK false, CANVAS false> leaves them
 };
 
 // ---------------------------------------------------------------- typed fast path

@@ -694,6 +694,10 @@ __global__ __launch_bounds__(256, MASK ? (MW > 0 ? MW : 1) : 8) void render_nn_k
   const double tp_nodata = tpp->nodata[ns_out];
   const int e0 = tpp->e0;
   const int W = tiles[t].width, H = tiles[t].height, pair_begin = tiles[t].pair_begin;
+  // tiles without a pair that the planner launches wrote (a.skip_pairless);
+  // a tile whose pairs all end outside the stack is still written here
+  bool pairless = false;
+  if constexpr (!MASK && !CANVAS) pairless = (a.skip_pairless != 0) & (pair_begin == tiles[t].pair_end);
   uint32_t col = 0;
   if constexpr (!CANVAS) col = a.ramp ? a.ramp[tid] : (0xFF000000u | ((uint32_t)tid * 0x10101u));
   const int band0 = (in_tile / col_blocks) * kRowsBlk;
@@ -702,7 +706,7 @@ __global__ __launch_bounds__(256, MASK ? (MW > 0 ? MW : 1) : 8) void render_nn_k
   // would sink the ones used later past it, one more latency each)
   asm volatile("" ::"s"((int)created), "s"(tp_dtype), "s"(__double_as_longlong(tp_nodata)), "s"(e0));
   // empty tiles: written here; bitwise, so that no branch splits the loads
-  if ((tp_complex != 0) | ((n_entries > 0) & (tp_vt != vt_code<T>())) | (band0 >= H) | (xb >= W)) return;
+  if ((tp_complex != 0) | ((n_entries > 0) & (tp_vt != vt_code<T>())) | (band0 >= H) | (xb >= W) | pairless) return;
   // ONE: the single entry's descriptor, loaded in the round after the tile's
   // (its index is the tile plan's e0) and before the palette barrier
   const EntryD *e1 = ents + max(e0, 0);
