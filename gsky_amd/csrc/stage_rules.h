@@ -1,7 +1,21 @@
 // stage_rules.h -- the per-value rules the stage kernels share: typed loads and
 // stores of a canvas element, Go's math.Log10 and the utils.Scale pixel rule
-// (raster_scaler.go:40-330).  One home, so stages.hip and fuse.hip compute the
-// same bits.
+// (raster_scaler.go:40-330).  One home for stages.hip and fuse.hip, which so
+// compute the same bits -- but not the rule's only copy.  utils.Scale is
+// written five times:
+//   S1  scale_one() here, with host_scale_consts() and the scale_minmax /
+//       scale_finalize / scale_apply kernels of stages.hip; fuse.hip's layers
+//       and outer scale
+//   S2  scale_px() + make_scale() + auto_minmax() (render_common.h): the
+//       general kernel, canvas_rgba_kernel after an auto-scale fold, float32
+//   S3  scale_t<T>() with go_u8_f32() (render_common.h): render_lds.h and the
+//       typed generic kernels (render_generic.h)
+//   S4  scale_int<T, SAFE>() (render_nn.h): the nearest-neighbour band kernel
+//   S5  scale_legacy_kernel (stages.hip): processor/tile_scaler.go
+// and Go's math.Log10 twice (go_log10_s here, go_log10 in render_common.h).
+// The render copies differ for register and speed reasons; what
+// holds all of them to the same bytes is tests/test_scale_edges.py, which
+// drives each with the case table of tests/test_scale_rule.py.
 #pragma once
 #include "gsky_device.h"
 #include "stages.h"
