@@ -3,7 +3,7 @@
 // Host side of the MI355X path: Go strconv mask parsing, the (path, band) ->
 // HBM granule registry behind the warp_operation_fast drop-in, and the launch
 // sequences (SRS parsing is crs.cpp's).  All pixel work runs in the HIP kernels
-// of render.hip / stages.hip / drill.hip; nothing here falls back to the CPU.
+// of plan.hip / render.hip / windows.hip / stages.hip / drill.hip; nothing here falls back to the CPU.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
 
@@ -1325,13 +1325,9 @@ int gskyhip_render_tiles(const gskyhip_granule *granules, int n_granules, const 
 }
 
 int gskyhip_render_status(void *workspace, int n_tiles, int n_pairs, int max_tile_height, void *stream) {
-  // TilePlan array position: after PairPlan[n_pairs] and Xform[n_pairs]
-  auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-  const int np = n_pairs > 0 ? n_pairs : 1;
-  const int64_t off = al(sizeof(PairPlan) * (int64_t)np) + al(sizeof(Xform) * (int64_t)np);
-  (void)max_tile_height;
-  std::vector<TilePlan> tp((size_t)(n_tiles > 0 ? n_tiles : 0));
   if (n_tiles <= 0) return 0;
+  const int64_t off = gsky::render_tile_plans_offset(n_tiles, n_pairs, max_tile_height);
+  std::vector<TilePlan> tp((size_t)n_tiles);
   if (hipMemcpyAsync(tp.data(), (char *)workspace + off, sizeof(TilePlan) * n_tiles, hipMemcpyDeviceToHost,
                      (hipStream_t)stream) != hipSuccess)
     return GSKYHIP_E_HIP;
@@ -1344,10 +1340,8 @@ int gskyhip_render_status(void *workspace, int n_tiles, int n_pairs, int max_til
 int gskyhip_render_tile_info(void *workspace, int n_tiles, int n_pairs, int max_tile_height, int32_t *info_out,
                              int32_t *counters_out, void *stream) {
   if (n_tiles < 0 || n_pairs < 0 || (n_tiles > 0 && (!workspace || !info_out))) return GSKYHIP_E_ARG;
-  auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
-  const int np = n_pairs > 0 ? n_pairs : 1;
-  const int64_t off = al(sizeof(PairPlan) * (int64_t)np) + al(sizeof(Xform) * (int64_t)np);
   if (n_tiles == 0) return 0;
+  const int64_t off = gsky::render_tile_plans_offset(n_tiles, n_pairs, max_tile_height);
   if (counters_out) {
     const int64_t c_off = gsky::render_counters_offset(n_tiles, n_pairs, max_tile_height);
     if (hipMemcpyAsync(counters_out, (char *)workspace + c_off, 3 * sizeof(int32_t), hipMemcpyDeviceToHost,

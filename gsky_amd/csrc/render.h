@@ -1,4 +1,7 @@
-// render.h -- host launchers of render.hip (batched GetMap path).
+// render.h -- the host launchers that host.cpp calls: the batched GetMap /
+// WCS render (render.hip), the `extent` op and the workspace accessors
+// (plan.hip), the FlexRaster windows and the service's warp batch with its
+// measurement hooks (windows.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -9,8 +12,11 @@ namespace gsky {
 
 struct MaskSpecS;
 
-int64_t render_counters_offset(int n_tiles, int n_pairs, int max_h);   // plan counters in the workspace
+// The workspace of a batch: its size, and the byte offsets of the plan
+// counters and of TilePlan[n_tiles] in it (the layout is carve()'s, plan.hip).
 int64_t render_workspace_size(int n_tiles, int n_pairs, int max_h);
+int64_t render_counters_offset(int n_tiles, int n_pairs, int max_h);
+int64_t render_tile_plans_offset(int n_tiles, int n_pairs, int max_h);
 
 // Shared planning: pairs, tiles, rows.  Returns 0 or an error.
 struct RenderCall {

@@ -1,6 +1,6 @@
 // render_common.h -- device-side pieces shared by the render kernels
-// (render.hip: planning + generic kernels; render_lds.hip: the typed
-// LDS-staged band kernel): ComputeMask bit tests, utils.Scale constants and
+// (render_generic.h: the generic kernels; band*.hip: the typed LDS-staged
+// band kernels; render.hip and windows.hip: their launchers): ComputeMask bit tests, utils.Scale constants and
 // conversions, the render argument block and the typed fast-path helpers.
 #pragma once
 #include <type_traits>
@@ -211,7 +211,7 @@ struct RenderArgs {
   const int64_t *cov_offsets;  // canvas mode: per tile element offset into one image (NULL: slots)
   int64_t cov_stride;          // ... and that image's row stride (elements)
   int skip_pairless;           // 1: the planner launches of this call wrote the tiles with pair_begin == pair_end
-                               // (render.hip, fill_pairless); render_nn_kernel<.., MASK false, CANVAS false> leaves them
+                               // (plan.hip, fill_pairless); render_nn_kernel<.., MASK false, CANVAS false> leaves them
 };
 
 // ---------------------------------------------------------------- typed fast path
@@ -521,7 +521,8 @@ constexpr int kSpline = 64, kLanczos = 128; // float32 canvases by a point kerne
 // The typed band kernels (render_lds.hip) for value type `vt`.
 void launch_band_kernels(const RenderArgs &a, int vt, bool mask, int n_items, hipStream_t s);
 // Generic kernels (render_generic{1,3}.hip); general_only: complex tiles only.
-void dispatch_render_1(const RenderArgs &a, int resample, bool mask, dim3 grid, bool general_only, hipStream_t s);
-void dispatch_render_3(const RenderArgs &a, int resample, bool mask, dim3 grid, bool general_only, hipStream_t s);
+// 0, or GSKYHIP_E_ARG when resample is no GSKYHIP_RESAMPLE_* value.
+int dispatch_render_1(const RenderArgs &a, int resample, bool mask, dim3 grid, bool general_only, hipStream_t s);
+int dispatch_render_3(const RenderArgs &a, int resample, bool mask, dim3 grid, bool general_only, hipStream_t s);
 
 }  // namespace gsky

@@ -1,8 +1,8 @@
 // render_generic.h -- per-pixel sampling (descend/exact/approx coordinates,
 // typed loads, the rules of resample.h over them) and the generic render
 // kernels (any value type, RGB or single namespace, auto-scale, complex
-// tiles).  Included by render.hip
-// (window / bytesRead kernels use the sampling helpers) and instantiated in
+// tiles).  Included by windows.hip (the window / bytesRead kernels use the
+// sampling helpers) and render.hip (auto-scale second pass), instantiated in
 // render_generic1.hip / render_generic3.hip so the NOUT=1 and NOUT=3 kernel
 // families compile as separate translation units.
 #pragma once
@@ -541,31 +541,16 @@ static void launch_render_kernels(const RenderArgs &a, dim3 grid, bool general_o
   hipLaunchKernelGGL((render_general_kernel<NOUT, RES, MASK>), dim3(gen_grid), dim3(256), 0, s, a);
 }
 
+// 0, or GSKYHIP_E_ARG (nothing launched) when resample is no rule.
 template <int NOUT>
-static void dispatch_render_t(const RenderArgs &a, int resample, bool mask, dim3 grid, bool general_only,
-                              hipStream_t s) {
-  if (resample == GSKYHIP_RESAMPLE_BILINEAR) {
-    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_BILINEAR, true>(a, grid, general_only, s);
-    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_BILINEAR, false>(a, grid, general_only, s);
-  } else if (resample == GSKYHIP_RESAMPLE_CUBIC) {
-    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBIC, true>(a, grid, general_only, s);
-    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBIC, false>(a, grid, general_only, s);
-  } else if (resample == GSKYHIP_RESAMPLE_AVERAGE) {
-    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_AVERAGE, true>(a, grid, general_only, s);
-    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_AVERAGE, false>(a, grid, general_only, s);
-  } else if (resample == GSKYHIP_RESAMPLE_MODE) {
-    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_MODE, true>(a, grid, general_only, s);
-    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_MODE, false>(a, grid, general_only, s);
-  } else if (resample == GSKYHIP_RESAMPLE_CUBICSPLINE) {
-    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBICSPLINE, true>(a, grid, general_only, s);
-    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_CUBICSPLINE, false>(a, grid, general_only, s);
-  } else if (resample == GSKYHIP_RESAMPLE_LANCZOS) {
-    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_LANCZOS, true>(a, grid, general_only, s);
-    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_LANCZOS, false>(a, grid, general_only, s);
-  } else {
-    if (mask) launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_NEAREST, true>(a, grid, general_only, s);
-    else launch_render_kernels<NOUT, GSKYHIP_RESAMPLE_NEAREST, false>(a, grid, general_only, s);
-  }
+static int dispatch_render_t(const RenderArgs &a, int resample, bool mask, dim3 grid, bool general_only,
+                             hipStream_t s) {
+  const bool known = with_resample(resample, [&](auto res) {
+    constexpr int RES = decltype(res)::value;
+    if (mask) launch_render_kernels<NOUT, RES, true>(a, grid, general_only, s);
+    else launch_render_kernels<NOUT, RES, false>(a, grid, general_only, s);
+  });
+  return known ? 0 : GSKYHIP_E_ARG;
 }
 
 }  // namespace gsky

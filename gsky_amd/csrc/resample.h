@@ -8,7 +8,8 @@
 // called only for taps inside the band: what a kernel loads, and how (typed
 // pointer, global address space, run-time source type), stays with the kernel.
 // A new resampler is one more *_rule() here over the same accessor, one more
-// branch in the callers' wrappers (render_common.h, render_generic.h).
+// branch in the callers' wrappers (render_common.h, render_generic.h) and one
+// more case of with_resample().
 #pragma once
 #include <type_traits>
 
@@ -26,7 +27,7 @@ __device__ __forceinline__ bool tap_is_nodata(double v, bool has_nodata, double 
 constexpr double kNnEps = 1.0e-10;
 
 // The rule along one axis of n source pixels, branch-free (bytesRead tests x
-// alone, render.hip); i is meaningful only where the result is true.
+// alone, windows.hip); i is meaningful only where the result is true.
 __device__ __forceinline__ bool nn_axis(double s, int n, int &i) {
   const double a = s + kNnEps;
   i = __double2int_rz(a);
@@ -215,6 +216,24 @@ constexpr bool is_area(int res) { return res == GSKYHIP_RESAMPLE_AVERAGE || res 
 // nearest neighbour under the area rules and the point kernels (bit fields
 // are neither averaged, voted nor convolved), else the data's.
 constexpr int mask_res(int res) { return (is_area(res) || is_kernel(res)) ? GSKYHIP_RESAMPLE_NEAREST : res; }
+
+// Host side: the run-time rule r as a compile-time one.  Calls
+// f(std::integral_constant<int, R>{}) for the GSKYHIP_RESAMPLE_* value r;
+// false, and no call, when r is none of them.  Every launch of a kernel
+// templated on the rule goes through here.
+template <class F>
+bool with_resample(int r, F &&f) {
+  switch (r) {
+    case GSKYHIP_RESAMPLE_NEAREST: f(std::integral_constant<int, GSKYHIP_RESAMPLE_NEAREST>{}); return true;
+    case GSKYHIP_RESAMPLE_BILINEAR: f(std::integral_constant<int, GSKYHIP_RESAMPLE_BILINEAR>{}); return true;
+    case GSKYHIP_RESAMPLE_CUBIC: f(std::integral_constant<int, GSKYHIP_RESAMPLE_CUBIC>{}); return true;
+    case GSKYHIP_RESAMPLE_AVERAGE: f(std::integral_constant<int, GSKYHIP_RESAMPLE_AVERAGE>{}); return true;
+    case GSKYHIP_RESAMPLE_MODE: f(std::integral_constant<int, GSKYHIP_RESAMPLE_MODE>{}); return true;
+    case GSKYHIP_RESAMPLE_CUBICSPLINE: f(std::integral_constant<int, GSKYHIP_RESAMPLE_CUBICSPLINE>{}); return true;
+    case GSKYHIP_RESAMPLE_LANCZOS: f(std::integral_constant<int, GSKYHIP_RESAMPLE_LANCZOS>{}); return true;
+    default: return false;
+  }
+}
 
 // Half extent of a footprint along one axis from that axis' component of
 // u = S(i + 1, row) - S(i, row) and v = S(i, row + 1) - S(i, row).

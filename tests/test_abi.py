@@ -37,6 +37,15 @@ def test_version(L):
     assert b"gfx950" in L.gskyhip_version()
 
 
+def test_render_workspace_size(L):
+    """The batch workspace (carve(), plan.hip) keeps its size: callers size
+    their buffers by it, and a change means the layout moved.  Values recorded
+    from the build before the planner got its own translation unit."""
+    for (n_tiles, n_pairs, max_h), size in [((0, 0, 256), 198912), ((1, 1, 1), 167936), ((1, 1, 256), 198912),
+                                            ((7, 33, 129), 738048), ((400, 3000, 256), 99364864)]:
+        assert L.gskyhip_render_workspace_size(n_tiles, n_pairs, max_h) == size, (n_tiles, n_pairs, max_h)
+
+
 def test_struct_sizes():
     from gsky_amd import _lib
     # layouts must match include/gskyhip.h (checked by a C compile below)

@@ -542,6 +542,57 @@ def test_compute_reproject_extent(gpu, oracle, dst):
         W.unregister_all()
 
 
+# (W, H, source, destination, geotransform, bbox, adjusted axis: 0 right / x, 1 bottom / y)
+BORDER_TRIAL_CASES = [
+    (100, 7, "EPSG:4326", "EPSG:3857", [131.5265740588777, 0.5, 0, -31.269165207466465, 0, -0.5],
+     [0.0, 0.0, 3.45e9, 3.45e9], 0),
+    (100, 7, "EPSG:3577", "EPSG:3857", [1772224.4222894707, 50000, 0, -2710353.5651497347, 0, -50000],
+     [0.0, 0.0, 3.45e9, 3.45e9], 0),
+    # also the 21 x 21 grid fallback: rows run past the pole
+    (512, 300, "EPSG:4326", "EPSG:3577", [131.5265740588777, 0.5, 0, -31.269165207466465, 0, -0.5],
+     [0.0, 0.0, 4.36e8, 4.36e8], 1),
+]
+
+
+def test_compute_reproject_extent_border_trials(gpu, oracle):
+    """GDALSuggestedWarpOutput2's right / bottom border adjustment beyond its
+    first trial (must_adjust / must_adjust2 over border_bad, plan.hip), which
+    the granules of test_compute_reproject_extent never take: zero-filled
+    int16 granules for which the oracle answers gt[1] != -gt[5] (one border
+    settled on a later trial), with a bbox of about 10^4 pixels so that the
+    0.1-1 % the trial changes the resolution by moves the pixel count.  The
+    extent op feeds psx / psy straight into the counts: a wrong trial is a
+    wrong integer."""
+    import torch
+
+    import gsky_amd.worker as W
+    prepared = []
+    for w, h, srs, dst, gt, bb, axis in BORDER_TRIAL_CASES:
+        data = np.zeros((h, w), np.int16)
+        og, src, dc = oracle.make_granule(data, gt), oracle.crs(srs), oracle.crs(dst)
+        rc, ogt, _, _, _ = oracle.suggested_warp_output(og, src, dc, [0.0, 1.0, 0.0, 0.0, 0.0, 1.0])
+        psx, psy = float(ogt[1]), -float(ogt[5])
+        assert rc == 0 and psx != psy, (srs, dst, psx, psy)
+        assert (psx < psy) == (axis == 0), (srs, dst, psx, psy)   # the adjusted border has the smaller pixel
+        exp = oracle.compute_reproject_extent(og, src, dc, bb)
+        big = max(psx, psy)   # the resolution before any adjustment
+        assert exp[axis] != int((bb[2 + axis] - bb[axis] + big / 2.0) / big), (srs, dst, exp)
+        prepared.append((data, srs, dst, gt, bb, exp))
+    assert {c[6] for c in BORDER_TRIAL_CASES} == {0, 1}
+    W.unregister_all()
+    try:
+        for k, (data, srs, dst, gt, bb, exp) in enumerate(prepared):
+            path = "NETCDF:/border%d.nc:band" % k
+            W.register_granule(path, 1, torch.from_numpy(data).cuda(), gt, srs, 0.0)
+            res = W.compute_reproject_extent(W.GeoRPCGranule(operation="extent", path=path, dstSRS=dst,
+                                                             dstGeot=list(bb)))
+            assert res.error == "OK" and res.raster.rasterType == "Int", (k, res.error)
+            got = tuple(int(v) for v in np.frombuffer(res.raster.data, dtype="<i8"))
+            assert got == exp, (k, srs, dst, got, exp)
+    finally:
+        W.unregister_all()
+
+
 def test_warp_operation_fast_dropin(gpu, oracle):
     """warp.go:82 drop-in through the worker mirror (WarpRaster)."""
     import torch

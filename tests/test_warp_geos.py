@@ -239,7 +239,7 @@ def test_limb_full_disc_world_tiles(gpu, z, x, y):
     at pixel 1.06, leaving column 0 (longitude -179.65, half a disc radius
     from the centre: 39 of their 269 required pixels each) outside it.  The
     planner closes the x extent to the destination's periodic edges in that
-    case (render.hip geos_seam), so these tiles hold the rule too.  MI355X:
+    case (plan.hip geos_seam), so these tiles hold the rule too.  MI355X:
     z0 3890 required, east tiles 7499, west tiles 269, none missing."""
     cfg = _limb_cfg([(synth._webmerc_tile_bbox(z, x, y), 256, 256)])
     _index_granules(cfg)
