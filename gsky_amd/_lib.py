@@ -130,6 +130,8 @@ EXPORTS = [
     "gskyhip_deflate_bound", "gskyhip_deflate_workspace_size", "gskyhip_deflate_blocks", "gskyhip_deflate_blocks_host",
     "gskyhip_encode_netcdf_deflate", "gskyhip_png_deflate_rows_host",
     "gskyhip_geotiff_bound_opts", "gskyhip_encode_geotiff_opts", "gskyhip_encode_geotiff_host",
+    "gskyhip_png_indexed_workspace_size", "gskyhip_png_indexed_bound", "gskyhip_encode_png_indexed",
+    "gskyhip_encode_png_indexed_host", "gskyhip_render_canvas_info",
 ]
 
 DECODE_HOST, DECODE_DEVICE = 0, 1
@@ -269,6 +271,14 @@ def lib() -> C.CDLL:
     L.gskyhip_png_bound.argtypes = [ci, ci]
     L.gskyhip_png_bound.restype = i64
     L.gskyhip_encode_png.argtypes = [vp, ci, ci, ci, i64, i64, vp, vp, i64, vp, i64, vp, ci, vp]
+    if hasattr(L, "gskyhip_encode_png_indexed"):   # absent from kept earlier builds (GSKYHIP_LIB=<name>)
+        L.gskyhip_png_indexed_workspace_size.argtypes = [ci, ci, ci]
+        L.gskyhip_png_indexed_workspace_size.restype = i64
+        L.gskyhip_png_indexed_bound.argtypes = [ci, ci]
+        L.gskyhip_png_indexed_bound.restype = i64
+        L.gskyhip_encode_png_indexed.argtypes = [vp, ci, ci, ci, i64, i64, vp, vp, vp, i64, vp, i64, vp, ci, vp]
+        L.gskyhip_encode_png_indexed_host.argtypes = [vp, ci, ci, vp, ci, vp, i64, vp]
+        L.gskyhip_render_canvas_info.argtypes = [vp, ci, ci, ci, vp, vp, vp]
     L.gskyhip_geotiff_workspace_size.argtypes = [ci, ci, ci, ci, ci, ci]
     L.gskyhip_geotiff_workspace_size.restype = i64
     L.gskyhip_geotiff_bound.argtypes = [ci, ci, ci, ci, ci, ci]

@@ -26,6 +26,28 @@
 // encoder's (or zlib's), not Go's compress/flate (all DEFLATE: the decoded
 // image and the filter bytes are identical, byte identity with Go is parity
 // unpinned).
+//
+// Beside it, opt-in and beyond the reference, the indexed-colour encoder for
+// one-band tiles (gskyhip_encode_png_indexed): EncodePNG expands
+// the ByteRaster of utils.Scale through the 256-entry ramp of
+// GradientRGBAPalette, or to grey, before png.Encode ever sees it; here the
+// index bytes themselves are the image data of a colour type 3 PNG --
+//   * IHDR (w, h, 8, 3, 0, 0, 0), PLTE, tRNS, IDAT..., IEND;
+//   * PLTE / tRNS entry i < 255: the color.NRGBAModel conversion above of
+//     ramp[i] (grey: i, i, i, 255); entry 255, the nodata byte 0xFF, is
+//     transparent black (ogc_encoders.go:96, 105), so every decoder gives the
+//     RGBA of the truecolour PNG of the same tile;
+//   * every row the filter byte 0 (None) and its w index bytes, no filter
+//     selection; the same GPU deflate with one byte a pixel, the same 32 KiB
+//     IDAT chunks, GSKYHIP_PNG_FIXED / GSKYHIP_PNG_ZLIB and the 4096-row limit.
+// Go's encoder never sees an image.Paletted on this path: the format is
+// defined here and parity with png.Encode of one is unpinned.  What ships:
+// two front ends -- png_opaque_kernel + png_filter_kernel for RGBA tiles,
+// png_index_rows_kernel for index tiles, which stages the rows, and PLTE /
+// tRNS framed once per call on the host -- over one back end (png_finish: the
+// tokenise / count / write kernels with the bytes a pixel per tile, 1, 3 or
+// 4, the IDAT CRC kernel, one copy of the compressed bytes, host framing),
+// and the indexed path's host twin gskyhip_encode_png_indexed_host.
 #include <hip/hip_runtime.h>
 #include <zlib.h>
 
@@ -47,10 +69,11 @@ namespace gsky {
 namespace {
 
 // ------------------------------------------------------------------ GPU pass
-// tile t opaque (image.RGBA.Opaque over its w x h rectangle)?
+// bytes a pixel of tile t: 3 when it is opaque (image.RGBA.Opaque over its
+// w x h rectangle: truecolour), else 4 (truecolour + alpha)
 __global__ __launch_bounds__(256) void png_opaque_kernel(const uint8_t *__restrict__ rgba, int64_t tile_stride,
                                                          int64_t row_stride, const int32_t *__restrict__ wh,
-                                                         int32_t *__restrict__ opaque) {
+                                                         int32_t *__restrict__ px_bytes) {
   const int t = blockIdx.x;
   const int w = wh[2 * t], h = wh[2 * t + 1];
   const uint8_t *base = rgba + (int64_t)t * tile_stride;
@@ -60,7 +83,7 @@ __global__ __launch_bounds__(256) void png_opaque_kernel(const uint8_t *__restri
     bad |= base[(int64_t)y * row_stride + 4 * x + 3] != 0xFF;
   }
   bad = __syncthreads_or(bad);
-  if (threadIdx.x == 0) opaque[t] = bad ? 0 : 1;
+  if (threadIdx.x == 0) px_bytes[t] = bad ? 4 : 3;
 }
 
 // byte k of row y of the image data Go's writeImage feeds the filter: RGB of
@@ -98,13 +121,13 @@ __device__ __forceinline__ uint32_t paeth(uint32_t a, uint32_t b, uint32_t c) { 
 // One workgroup per (tile, row): out row = [filter byte][filtered bytes].
 __global__ __launch_bounds__(256) void png_filter_kernel(const uint8_t *__restrict__ rgba, int64_t tile_stride,
                                                          int64_t row_stride, const int32_t *__restrict__ wh,
-                                                         const int32_t *__restrict__ opaque, int max_h,
+                                                         const int32_t *__restrict__ px_bytes, int max_h,
                                                          const int64_t *__restrict__ out_off,
                                                          uint8_t *__restrict__ out) {
   const int t = blockIdx.x / max_h, y = blockIdx.x % max_h;
   const int w = wh[2 * t], h = wh[2 * t + 1];
   if (y >= h) return;
-  const bool opq = opaque[t] != 0;
+  const bool opq = px_bytes[t] == 3;
   const int bpp = opq ? 3 : 4;
   const int n = bpp * w;
   const uint8_t *tile = rgba + (int64_t)t * tile_stride;
@@ -155,6 +178,42 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const uint8_t *__restri
   }
 }
 
+// Indexed colour: the image data of tile t -- h rows of [filter byte 0][the
+// row's w index bytes] -- packed at out + t * per, from a tile whose rows lie
+// row_stride bytes apart.  A thread per aligned dword of the packed stream
+// (per is a multiple of 4 and out 4-byte aligned, so the store is one dword
+// and a wave stores 256 consecutive bytes): where the four bytes are pixels of
+// one row they are one load, the filter byte having shifted them by y + 1
+// bytes against the source row, hence unaligned; a dword that holds a filter
+// byte, straddles two rows or ends the stream is put together from bytes.
+// Bytes of the last dword past the stream are zero.  Reads stay inside the
+// tile's w x h rectangle, writes below out + t * per + per.
+__global__ __launch_bounds__(256) void png_index_rows_kernel(const uint8_t *__restrict__ index, int64_t tile_stride,
+                                                             int64_t row_stride, const int32_t *__restrict__ wh,
+                                                             int blocks_per_tile, int64_t per,
+                                                             uint8_t *__restrict__ out) {
+  const int t = (int)(blockIdx.x / (unsigned)blocks_per_tile);
+  const int64_t q = ((int64_t)(blockIdx.x % (unsigned)blocks_per_tile) * 256 + threadIdx.x) * 4;
+  const int w = wh[2 * t], h = wh[2 * t + 1];
+  const int stride = 1 + w;
+  const int64_t n = (int64_t)h * stride;
+  if (q >= n) return;
+  const uint8_t *tile = index + (int64_t)t * tile_stride;
+  // row and column (0: the filter byte) of stream byte q; 32-bit division where the stream allows
+  int64_t y = n <= 0x7FFFFFFF ? (int64_t)((uint32_t)q / (uint32_t)stride) : q / stride;
+  int c = (int)(q - y * stride);
+  uint32_t v = 0;
+  if (c >= 1 && c + 3 < stride) {
+    v = deflate::ld_u32(tile + y * row_stride + (c - 1));
+  } else {
+    for (int k = 0; k < 4 && q + k < n; k++) {
+      if (c != 0) v |= (uint32_t)tile[y * row_stride + (c - 1)] << (8 * k);
+      if (++c == stride) { c = 0; y++; }
+    }
+  }
+  *(uint32_t *)(out + (int64_t)t * per + q) = v;
+}
+
 // ------------------------------------------------------------------ GPU deflate
 // The zlib stream of each tile's filtered rows built on the GPU: one final
 // block -- Huffman codes built for the tile from its symbol frequencies
@@ -187,13 +246,13 @@ constexpr int kPngMaxRows = 4096;    // rows of a tile the deflate kernels handl
 __global__ __launch_bounds__(64) void png_tokenize_kernel(const uint8_t *__restrict__ filt,
                                                           const int64_t *__restrict__ off,
                                                           const int32_t *__restrict__ wh,
-                                                          const int32_t *__restrict__ opaque, int max_h,
+                                                          const int32_t *__restrict__ px_bytes, int max_h,
                                                           uint32_t *__restrict__ tok, int32_t *__restrict__ ntok,
                                                           int64_t per, uint32_t *__restrict__ freq, int dynamic) {
   const int groups = (max_h + 63) / 64;
   const int t = (int)(blockIdx.x / groups), tid = threadIdx.x, y = (int)(blockIdx.x % groups) * 64 + tid;
   const int h = wh[2 * t + 1];
-  const int bpp = opaque[t] ? 3 : 4;
+  const int bpp = px_bytes[t];
   const int stride = 1 + bpp * wh[2 * t];
   __shared__ uint32_t s_freq[gd::kSymN];
   for (int i = tid; i < gd::kSymN; i += 64) s_freq[i] = 0;
@@ -221,7 +280,7 @@ static_assert(sizeof(gd::Plan) % 4 == 0, "a tile's plan is copied in dwords");
 __global__ __launch_bounds__(256) void png_deflate_count_kernel(const uint8_t *__restrict__ filt,
                                                                 const int64_t *__restrict__ off,
                                                                 const int32_t *__restrict__ wh,
-                                                                const int32_t *__restrict__ opaque, int max_h,
+                                                                const int32_t *__restrict__ px_bytes, int max_h,
                                                                 int32_t *__restrict__ row_bits,
                                                                 uint32_t *__restrict__ adler,
                                                                 int64_t *__restrict__ zlen, gd::Plan *__restrict__ tab,
@@ -230,7 +289,7 @@ __global__ __launch_bounds__(256) void png_deflate_count_kernel(const uint8_t *_
                                                                 const uint32_t *__restrict__ freq) {
   const int t = blockIdx.x, tid = threadIdx.x;
   const int w = wh[2 * t], h = wh[2 * t + 1];
-  const int bpp = opaque[t] ? 3 : 4;
+  const int bpp = px_bytes[t];
   const int stride = 1 + bpp * w;
   const uint8_t *data = filt + off[t];
   __shared__ uint32_t s_a[kPngMaxRows], s_b[kPngMaxRows];
@@ -289,7 +348,7 @@ __global__ __launch_bounds__(256) void png_deflate_count_kernel(const uint8_t *_
 // in the tile's stream, at the tile's byte offset zoff[t] of the packed buffer
 // (zeroed; 4-byte aligned, so the stream is the sink's words).
 __global__ __launch_bounds__(256) void png_deflate_write_kernel(const int32_t *__restrict__ wh,
-                                                                const int32_t *__restrict__ opaque, int max_h,
+                                                                const int32_t *__restrict__ px_bytes, int max_h,
                                                                 const int32_t *__restrict__ row_bits,
                                                                 const uint32_t *__restrict__ adler,
                                                                 const int64_t *__restrict__ zoff,
@@ -299,7 +358,7 @@ __global__ __launch_bounds__(256) void png_deflate_write_kernel(const int32_t *_
                                                                 const int32_t *__restrict__ ntok, int64_t per) {
   const int t = blockIdx.x;
   const int w = wh[2 * t], h = wh[2 * t + 1];
-  const int stride = 1 + (opaque[t] ? 3 : 4) * w;
+  const int stride = 1 + px_bytes[t] * w;
   uint32_t *words = (uint32_t *)(packed + zoff[t]);
   __shared__ int64_t s_start[kPngMaxRows];
   __shared__ uint16_t s_code[gd::kSymN];
@@ -398,8 +457,43 @@ void chunk(std::vector<uint8_t> &o, const char *type, const uint8_t *data, size_
   put32(o, (uint32_t)crc32(0L, o.data() + at, (uInt)(n + 4)));
 }
 
-// PNG signature + IHDR of a w x h 8-bit truecolour (alpha) image.
-void png_head(int w, int h, bool opq, std::vector<uint8_t> &o) {
+// How a call's tiles are framed.  Truecolour (gskyhip_encode_png): pal is
+// NULL and a tile's colour type follows its bytes a pixel, 3 -> RGB (2),
+// 4 -> RGBA (6).  Indexed (gskyhip_encode_png_indexed): colour type 3, and
+// pal is the PLTE and tRNS chunks that follow every IHDR, framed once.
+int png_colour_type(int px_bytes) { return px_bytes == 1 ? 3 : px_bytes == 3 ? 2 : 6; }
+
+// byte c (0..2) of the color.NRGBAModel conversion of a premultiplied RGBA
+// entry: png_byte()'s rule on the host
+uint8_t nrgba_byte(const uint8_t *px, int c) {
+  const uint32_t a = px[3];
+  if (a == 0xFF) return px[c];
+  if (a == 0) return 0;
+  const uint32_t a16 = a | (a << 8);
+  const uint32_t v16 = (uint32_t)px[c] | ((uint32_t)px[c] << 8);
+  return (uint8_t)(((v16 * 0xFFFFu) / a16 >> 8) & 0xFFu);
+}
+
+// PLTE and tRNS of an indexed call, with length, type and CRC-32: entry i <
+// 255 is the NRGBA of ramp[i] (256 x RGBA as GradientRGBAPalette leaves it),
+// or (i, i, i, 255) without a ramp (grey); entry 255, the nodata index, is
+// transparent black (ogc_encoders.go:96, 105).
+void png_palette_chunks(const uint8_t *ramp, std::vector<uint8_t> &o) {
+  uint8_t plte[768], trns[256];
+  for (int i = 0; i < 255; i++) {
+    for (int c = 0; c < 3; c++) plte[3 * i + c] = ramp ? nrgba_byte(ramp + 4 * i, c) : (uint8_t)i;
+    trns[i] = ramp ? ramp[4 * i + 3] : 0xFF;
+  }
+  plte[765] = plte[766] = plte[767] = 0;
+  trns[255] = 0;
+  o.clear();
+  chunk(o, "PLTE", plte, 768);
+  chunk(o, "tRNS", trns, 256);
+}
+
+// PNG signature + IHDR of a w x h 8-bit image of px_bytes a pixel, then the
+// call's palette chunks, if any.
+void png_head(int w, int h, int px_bytes, const std::vector<uint8_t> *pal, std::vector<uint8_t> &o) {
   static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1A, '\n'};
   o.assign(sig, sig + 8);
   uint8_t ihdr[13];
@@ -407,19 +501,20 @@ void png_head(int w, int h, bool opq, std::vector<uint8_t> &o) {
   ihdr[0] = ww >> 24; ihdr[1] = ww >> 16; ihdr[2] = ww >> 8; ihdr[3] = ww;
   ihdr[4] = hh >> 24; ihdr[5] = hh >> 16; ihdr[6] = hh >> 8; ihdr[7] = hh;
   ihdr[8] = 8;                 // bit depth
-  ihdr[9] = opq ? 2 : 6;       // truecolour / truecolour + alpha
+  ihdr[9] = (uint8_t)png_colour_type(px_bytes);   // truecolour / truecolour + alpha / indexed
   ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
   chunk(o, "IHDR", ihdr, 13);
+  if (pal) o.insert(o.end(), pal->begin(), pal->end());
 }
 
 // A whole PNG around a finished zlib stream, written straight into dst
 // (cap bytes): 32 KiB IDAT chunks (Go's bufio.Writer size), IEND; returns
 // its size, 0 when it does not fit.
-size_t png_frame(const uint8_t *z, size_t zn, int w, int h, bool opq, uint8_t *dst, size_t cap,
-                 const uint32_t *idat_crc) {
+size_t png_frame(const uint8_t *z, size_t zn, int w, int h, int px_bytes, const std::vector<uint8_t> *pal,
+                 uint8_t *dst, size_t cap, const uint32_t *idat_crc) {
   std::vector<uint8_t> head;
-  png_head(w, h, opq, head);
-  const size_t need = head.size() + (zn / 32768 + 1) * 12 + zn + 12;
+  png_head(w, h, px_bytes, pal, head);
+  const size_t need = head.size() + (zn + 32767) / 32768 * 12 + zn + 12;
   if (need > cap) return 0;
   uint8_t *o = dst;
   std::memcpy(o, head.data(), head.size());
@@ -442,10 +537,11 @@ size_t png_frame(const uint8_t *z, size_t zn, int w, int h, bool opq, uint8_t *d
   return (size_t)(o - dst);
 }
 
-// One tile through host zlib: PNG signature, IHDR, the zlib stream in 32 KiB
-// IDAT chunks, IEND.
-int png_tile(const uint8_t *filtered, size_t n_filtered, int w, int h, bool opq, std::vector<uint8_t> &o) {
-  png_head(w, h, opq, o);
+// One tile through host zlib: PNG signature, IHDR, the palette chunks, the
+// zlib stream in 32 KiB IDAT chunks, IEND.
+int png_tile(const uint8_t *filtered, size_t n_filtered, int w, int h, int px_bytes, const std::vector<uint8_t> *pal,
+             std::vector<uint8_t> &o) {
+  png_head(w, h, px_bytes, pal, o);
   std::vector<uint8_t> z(compressBound((uLong)n_filtered) + 64);
   z_stream s;
   std::memset(&s, 0, sizeof(s));
@@ -470,31 +566,6 @@ using namespace gsky;
 
 extern "C" {
 
-// Workspace: filtered rows | per-tile offsets, sizes, opacity | per-row bit
-// counts | Adler-32, zlib lengths and offsets | per-tile codes | the packed
-// zlib streams (at most 9/8 of the filtered bytes + 16 per tile: a dynamic
-// block is only used where it is shorter than the fixed one) | the rows'
-// tokens (a dword per filtered byte at most) and token counts.
-static int64_t png_deflate_cap(int64_t per) { return (per * 9 + 7) / 8 + 64 + (per / 32768 + 1) * 4 + 256; }
-
-int64_t gskyhip_png_workspace_size(int n_tiles, int max_w, int max_h) {
-  if (n_tiles <= 0 || max_w <= 0 || max_h <= 0) return 0;
-  const int64_t per = (int64_t)max_h * (1 + 4 * (int64_t)max_w);
-  const int64_t a = ((int64_t)n_tiles * per + 255) / 256 * 256 + (int64_t)n_tiles * (8 + 8 + 4) + 1024;
-  const int64_t b = ((int64_t)n_tiles * max_h * 4 + 255) / 256 * 256 + (int64_t)n_tiles * (4 + 8 + 8) + 1024 +
-                    (int64_t)n_tiles * (int64_t)sizeof(deflate::Plan) + 256;
-  const int64_t c = (int64_t)n_tiles * per * 4 + (int64_t)n_tiles * max_h * 4 + 1024 +   // tokens, counts,
-                    (int64_t)n_tiles * deflate::kSymN * 4 + 256;                                 // symbol frequencies
-  return a + b + (int64_t)n_tiles * png_deflate_cap(per) + 1024 + c;
-}
-
-int64_t gskyhip_png_bound(int width, int height) {
-  if (width <= 0 || height <= 0) return 0;
-  const uLong raw = (uLong)height * (1 + 4 * (uLong)width);
-  const uLong z = std::max<uLong>(compressBound(raw) + 64, (uLong)png_deflate_cap((int64_t)raw));
-  return 8 + 25 + (int64_t)(z / 32768 + 1) * 12 + (int64_t)z + 12;
-}
-
 int gskyhip_png_deflate_rows_host(const uint8_t *rows, int h, int stride, int bpp, int fixed_only, uint8_t *out,
                                   int64_t cap, int64_t *out_len) {
   if (!rows || !out || !out_len || h <= 0 || stride <= 0 || (bpp != 3 && bpp != 4) || cap < 0 ||
@@ -507,37 +578,112 @@ int gskyhip_png_deflate_rows_host(const uint8_t *rows, int h, int stride, int bp
   }
 }
 
-int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, int64_t tile_stride,
-                       int64_t row_stride, const int32_t *sizes, void *workspace, int64_t workspace_bytes,
-                       uint8_t *png_out, int64_t png_capacity, int64_t *png_sizes, int n_threads, void *stream) {
-  if (n_tiles <= 0) return 0;
-  if (!rgba || !sizes || !png_out || !png_sizes || max_w <= 0 || max_h <= 0 || row_stride < 4LL * max_w ||
-      tile_stride < row_stride * max_h)
-    return GSKYHIP_E_ARG;
-  if (!workspace || workspace_bytes < gskyhip_png_workspace_size(n_tiles, max_w, max_h)) return GSKYHIP_E_ARG;
-  for (int t = 0; t < n_tiles; t++) {
-    const int w = sizes[2 * t], h = sizes[2 * t + 1];
-    if (w <= 0 || h <= 0 || w > max_w || h > max_h || png_capacity < gskyhip_png_bound(w, h)) return GSKYHIP_E_ARG;
+// Workspace: the rows (filtered, or staged index rows) | per-tile offsets,
+// sizes, bytes a pixel | per-row bit counts | Adler-32, zlib lengths and
+// offsets | per-tile codes | the packed zlib streams (at most 9/8 of the
+// rows' bytes + 16 per tile: a dynamic block is only used where it is
+// shorter than the fixed one) | the rows' tokens (a dword per byte at most)
+// and token counts.  `per` is a tile's slot of row bytes: max_h * (1 + 4 *
+// max_w) for truecolour, max_h * (1 + max_w) in whole dwords for indexed.
+static int64_t png_deflate_cap(int64_t per) { return (per * 9 + 7) / 8 + 64 + (per / 32768 + 1) * 4 + 256; }
+
+static int64_t png_workspace(int n_tiles, int max_h, int64_t per) {
+  const int64_t a = ((int64_t)n_tiles * per + 255) / 256 * 256 + (int64_t)n_tiles * (8 + 8 + 4) + 1024;
+  const int64_t b = ((int64_t)n_tiles * max_h * 4 + 255) / 256 * 256 + (int64_t)n_tiles * (4 + 8 + 8) + 1024 +
+                    (int64_t)n_tiles * (int64_t)sizeof(deflate::Plan) + 256;
+  const int64_t c = (int64_t)n_tiles * per * 4 + (int64_t)n_tiles * max_h * 4 + 1024 +   // tokens, counts,
+                    (int64_t)n_tiles * deflate::kSymN * 4 + 256;                                 // symbol frequencies
+  return a + b + (int64_t)n_tiles * png_deflate_cap(per) + 1024 + c;
+}
+
+// the most bytes of a PNG over `raw` bytes of rows, `extra` bytes of chunks between IHDR and IDAT
+static int64_t png_bound(int64_t raw, int64_t extra) {
+  const uLong z = std::max<uLong>(compressBound((uLong)raw) + 64, (uLong)png_deflate_cap(raw));
+  return 8 + 25 + extra + (int64_t)(z / 32768 + 1) * 12 + (int64_t)z + 12;
+}
+
+int64_t gskyhip_png_workspace_size(int n_tiles, int max_w, int max_h) {
+  if (n_tiles <= 0 || max_w <= 0 || max_h <= 0) return 0;
+  return png_workspace(n_tiles, max_h, (int64_t)max_h * (1 + 4 * (int64_t)max_w));
+}
+
+int64_t gskyhip_png_bound(int width, int height) {
+  if (width <= 0 || height <= 0) return 0;
+  return png_bound((int64_t)height * (1 + 4 * (int64_t)width), 0);
+}
+
+// An indexed tile's slot of the workspace: its rows of 1 + w bytes, rounded up
+// to whole dwords (png_index_rows_kernel stores dwords)
+static int64_t png_indexed_per(int max_w, int max_h) { return ((int64_t)max_h * (1 + (int64_t)max_w) + 3) & ~(int64_t)3; }
+
+int64_t gskyhip_png_indexed_workspace_size(int n_tiles, int max_w, int max_h) {
+  if (n_tiles <= 0 || max_w <= 0 || max_h <= 0) return 0;
+  return png_workspace(n_tiles, max_h, png_indexed_per(max_w, max_h));
+}
+
+int64_t gskyhip_png_indexed_bound(int width, int height) {
+  if (width <= 0 || height <= 0) return 0;
+  return png_bound((int64_t)height * (1 + (int64_t)width), (12 + 768) + (12 + 256));   // + PLTE, tRNS
+}
+
+// What both encoders hand to png_finish: the call's arguments and the head of
+// its workspace -- the rows of tile t at filt + t * per, then (d_off) the
+// tiles' offsets, sizes and bytes a pixel.
+struct PngCall {
+  int n_tiles, max_h;
+  int64_t per;
+  const int32_t *sizes;
+  const std::vector<uint8_t> *pal;   // PLTE + tRNS (indexed), or NULL
+  char *ws;
+  int64_t workspace_bytes;
+  uint8_t *png_out;
+  int64_t png_capacity;
+  int64_t *png_sizes;
+  int n_threads;
+  hipStream_t s;
+  uint8_t *filt;
+  char *tail;
+  int64_t *d_off;
+  int32_t *d_wh, *d_px;
+  std::vector<char> meta;            // the upload's source, alive until the call has synchronised
+};
+
+// carves the head of the workspace and uploads the offsets and sizes; px_bytes
+// != 0: also that value as every tile's bytes a pixel (else a kernel sets them)
+static int png_begin(PngCall &c, int px_bytes) {
+  const int n_tiles = c.n_tiles;
+  c.filt = (uint8_t *)c.ws;
+  c.tail = c.ws + ((int64_t)n_tiles * c.per + 255) / 256 * 256;
+  c.d_off = (int64_t *)c.tail;
+  c.d_wh = (int32_t *)(c.d_off + n_tiles);
+  c.d_px = c.d_wh + 2 * n_tiles;
+  std::vector<char> &meta = c.meta;
+  meta.resize((size_t)n_tiles * (8 + 8 + (px_bytes ? 4 : 0)));
+  int64_t *off = (int64_t *)meta.data();
+  for (int t = 0; t < n_tiles; t++) off[t] = (int64_t)t * c.per;
+  std::memcpy(meta.data() + (size_t)n_tiles * 8, c.sizes, (size_t)n_tiles * 8);
+  if (px_bytes) {
+    int32_t *px = (int32_t *)(meta.data() + (size_t)n_tiles * 16);
+    for (int t = 0; t < n_tiles; t++) px[t] = px_bytes;
   }
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t per = (int64_t)max_h * (1 + 4 * (int64_t)max_w);
-  char *ws = (char *)workspace;
-  uint8_t *filt = (uint8_t *)ws;
-  char *tail = ws + ((int64_t)n_tiles * per + 255) / 256 * 256;
-  int64_t *d_off = (int64_t *)tail;
-  int32_t *d_wh = (int32_t *)(d_off + n_tiles);
-  int32_t *d_opq = d_wh + 2 * n_tiles;
-  std::vector<int64_t> off(n_tiles);
-  for (int t = 0; t < n_tiles; t++) off[t] = (int64_t)t * per;
-  std::vector<char> meta((size_t)n_tiles * (8 + 8));
-  std::memcpy(meta.data(), off.data(), (size_t)n_tiles * 8);
-  std::memcpy(meta.data() + (size_t)n_tiles * 8, sizes, (size_t)n_tiles * 8);
-  if (hipMemcpyAsync(d_off, meta.data(), meta.size(), hipMemcpyHostToDevice, s) != hipSuccess) return GSKYHIP_E_HIP;
-  hipLaunchKernelGGL(png_opaque_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, rgba, tile_stride, row_stride, d_wh,
-                     d_opq);
-  hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)((int64_t)n_tiles * max_h)), dim3(256), 0, s, rgba,
-                     tile_stride, row_stride, d_wh, d_opq, max_h, d_off, filt);
-  if (hipGetLastError() != hipSuccess) return GSKYHIP_E_HIP;
+  return hipMemcpyAsync(c.d_off, meta.data(), meta.size(), hipMemcpyHostToDevice, c.s) == hipSuccess ? 0
+                                                                                                       : GSKYHIP_E_HIP;
+}
+
+// Everything behind the rows: the GPU deflate of every tile, the CRC-32 of its
+// IDAT chunks, one copy of the compressed bytes and the framing on host
+// threads; or, for tiles of more than kPngMaxRows rows and under
+// GSKYHIP_PNG_ZLIB=1, a copy of the rows and host zlib.
+static int png_finish(const PngCall &c) {
+  const int n_tiles = c.n_tiles, max_h = c.max_h, n_threads = c.n_threads;
+  const int64_t per = c.per, workspace_bytes = c.workspace_bytes, png_capacity = c.png_capacity;
+  const int32_t *sizes = c.sizes;
+  const std::vector<uint8_t> *pal = c.pal;
+  char *ws = c.ws, *tail = c.tail;
+  uint8_t *png_out = c.png_out, *filt = c.filt;
+  int64_t *png_sizes = c.png_sizes, *d_off = c.d_off;
+  int32_t *d_wh = c.d_wh, *d_px = c.d_px;
+  hipStream_t s = c.s;
   // GSKYHIP_PNG_ZLIB=1: deflate with zlib level 6 on host threads (round 3)
   const char *zl = std::getenv("GSKYHIP_PNG_ZLIB");
   const bool host_zlib = zl && std::atoi(zl) != 0;
@@ -566,14 +712,14 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
     if ((char *)(d_freq + (int64_t)n_tiles * deflate::kSymN) > ws + workspace_bytes) return GSKYHIP_E_ARG;
     if (hipMemsetAsync(d_freq, 0, (size_t)n_tiles * deflate::kSymN * 4, s) != hipSuccess) return GSKYHIP_E_HIP;
     hipLaunchKernelGGL(png_tokenize_kernel, dim3((unsigned)((int64_t)n_tiles * ((max_h + 63) / 64))), dim3(64), 0, s, filt,
-                       d_off, d_wh, d_opq, max_h, d_tok, d_ntok, per, d_freq, dynamic);
-    hipLaunchKernelGGL(png_deflate_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, filt, d_off, d_wh, d_opq,
+                       d_off, d_wh, d_px, max_h, d_tok, d_ntok, per, d_freq, dynamic);
+    hipLaunchKernelGGL(png_deflate_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, filt, d_off, d_wh, d_px,
                        max_h, d_rowbits, d_adler, d_zlen, d_tab, dynamic, d_tok, d_ntok, per, d_freq);
     std::vector<int64_t> zlen(n_tiles), zoff(n_tiles);
-    std::vector<int32_t> opq(n_tiles);
+    std::vector<int32_t> px(n_tiles);
     if (hipGetLastError() != hipSuccess ||
         hipMemcpyAsync(zlen.data(), d_zlen, (size_t)n_tiles * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(opq.data(), d_opq, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(px.data(), d_px, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess)
       return GSKYHIP_E_HIP;
     const double t_count = now_us();
@@ -587,7 +733,7 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
     if (hipMemcpyAsync(d_zoff, zoff.data(), (size_t)n_tiles * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemsetAsync(d_packed, 0, (size_t)std::max<int64_t>(total, 4), s) != hipSuccess)
       return GSKYHIP_E_HIP;
-    hipLaunchKernelGGL(png_deflate_write_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, d_wh, d_opq, max_h,
+    hipLaunchKernelGGL(png_deflate_write_kernel, dim3((unsigned)n_tiles), dim3(256), 0, s, d_wh, d_px, max_h,
                        d_rowbits, d_adler, d_zoff, d_packed, d_tab, d_tok, d_ntok, per);
     // IDAT CRCs behind the packed streams (the pinned read-back holds both)
     const int64_t crc_at = (total + 255) & ~(int64_t)255;
@@ -616,7 +762,7 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
       for (;;) {
         const int t = next++;
         if (t >= n_tiles) return;
-        const size_t n = png_frame(zhost + zoff[t], (size_t)zlen[t], sizes[2 * t], sizes[2 * t + 1], opq[t] != 0,
+        const size_t n = png_frame(zhost + zoff[t], (size_t)zlen[t], sizes[2 * t], sizes[2 * t + 1], px[t], pal,
                                    png_out + (int64_t)t * png_capacity, (size_t)png_capacity,
                                    (const uint32_t *)(zhost + crc_at) + (int64_t)t * max_chunks);
         if (!n) err = GSKYHIP_E_ARG;
@@ -635,9 +781,9 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
     return err.load();
   }
   std::vector<uint8_t> host((size_t)n_tiles * per);
-  std::vector<int32_t> opq(n_tiles);
+  std::vector<int32_t> px(n_tiles);
   if (hipMemcpyAsync(host.data(), filt, host.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(opq.data(), d_opq, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(px.data(), d_px, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return GSKYHIP_E_HIP;
   // deflate + framing per tile on host threads
@@ -648,8 +794,8 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
       const int t = next++;
       if (t >= n_tiles) return;
       const int w = sizes[2 * t], h = sizes[2 * t + 1];
-      const size_t n = (size_t)h * (1 + (opq[t] ? 3 : 4) * (size_t)w);
-      const int rc = png_tile(host.data() + off[t], n, w, h, opq[t] != 0, o);
+      const size_t n = (size_t)h * (1 + (size_t)px[t] * (size_t)w);
+      const int rc = png_tile(host.data() + (int64_t)t * per, n, w, h, px[t], pal, o);
       if (rc || (int64_t)o.size() > png_capacity) { err = rc ? rc : GSKYHIP_E_ARG; png_sizes[t] = 0; continue; }
       std::memcpy(png_out + (int64_t)t * png_capacity, o.data(), o.size());
       png_sizes[t] = (int64_t)o.size();
@@ -661,6 +807,95 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
   work();
   for (auto &th : pool) th.join();
   return err.load();
+}
+
+int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, int64_t tile_stride,
+                       int64_t row_stride, const int32_t *sizes, void *workspace, int64_t workspace_bytes,
+                       uint8_t *png_out, int64_t png_capacity, int64_t *png_sizes, int n_threads, void *stream) {
+  if (n_tiles <= 0) return 0;
+  if (!rgba || !sizes || !png_out || !png_sizes || max_w <= 0 || max_h <= 0 || row_stride < 4LL * max_w ||
+      tile_stride < row_stride * max_h)
+    return GSKYHIP_E_ARG;
+  if (!workspace || workspace_bytes < gskyhip_png_workspace_size(n_tiles, max_w, max_h)) return GSKYHIP_E_ARG;
+  for (int t = 0; t < n_tiles; t++) {
+    const int w = sizes[2 * t], h = sizes[2 * t + 1];
+    if (w <= 0 || h <= 0 || w > max_w || h > max_h || png_capacity < gskyhip_png_bound(w, h)) return GSKYHIP_E_ARG;
+  }
+  PngCall c;
+  c.n_tiles = n_tiles; c.max_h = max_h; c.per = (int64_t)max_h * (1 + 4 * (int64_t)max_w);
+  c.sizes = sizes; c.pal = nullptr; c.ws = (char *)workspace; c.workspace_bytes = workspace_bytes;
+  c.png_out = png_out; c.png_capacity = png_capacity; c.png_sizes = png_sizes; c.n_threads = n_threads;
+  c.s = (hipStream_t)stream;
+  if (png_begin(c, 0)) return GSKYHIP_E_HIP;
+  hipLaunchKernelGGL(png_opaque_kernel, dim3((unsigned)n_tiles), dim3(256), 0, c.s, rgba, tile_stride, row_stride,
+                     c.d_wh, c.d_px);
+  hipLaunchKernelGGL(png_filter_kernel, dim3((unsigned)((int64_t)n_tiles * max_h)), dim3(256), 0, c.s, rgba,
+                     tile_stride, row_stride, c.d_wh, c.d_px, max_h, c.d_off, c.filt);
+  if (hipGetLastError() != hipSuccess) return GSKYHIP_E_HIP;
+  return png_finish(c);
+}
+
+// The indexed encoder: png_index_rows_kernel stages the rows, PLTE and tRNS
+// are framed once on the host, and png_finish does the rest with one byte a
+// pixel.
+int gskyhip_encode_png_indexed(const uint8_t *index, int n_tiles, int max_w, int max_h, int64_t tile_stride,
+                               int64_t row_stride, const int32_t *sizes, const uint8_t *ramp, void *workspace,
+                               int64_t workspace_bytes, uint8_t *png_out, int64_t png_capacity,
+                               int64_t *png_sizes, int n_threads, void *stream) {
+  if (n_tiles <= 0) return 0;
+  if (!index || !sizes || !png_out || !png_sizes || max_w <= 0 || max_h <= 0 || row_stride < (int64_t)max_w ||
+      tile_stride < row_stride * max_h)
+    return GSKYHIP_E_ARG;
+  if (!workspace || ((uintptr_t)workspace & 7) ||
+      workspace_bytes < gskyhip_png_indexed_workspace_size(n_tiles, max_w, max_h))
+    return GSKYHIP_E_ARG;
+  for (int t = 0; t < n_tiles; t++) {
+    const int w = sizes[2 * t], h = sizes[2 * t + 1];
+    if (w <= 0 || h <= 0 || w > max_w || h > max_h || png_capacity < gskyhip_png_indexed_bound(w, h))
+      return GSKYHIP_E_ARG;
+  }
+  std::vector<uint8_t> pal;
+  png_palette_chunks(ramp, pal);
+  PngCall c;
+  c.n_tiles = n_tiles; c.max_h = max_h; c.per = png_indexed_per(max_w, max_h);
+  c.sizes = sizes; c.pal = &pal; c.ws = (char *)workspace; c.workspace_bytes = workspace_bytes;
+  c.png_out = png_out; c.png_capacity = png_capacity; c.png_sizes = png_sizes; c.n_threads = n_threads;
+  c.s = (hipStream_t)stream;
+  const int64_t blocks_per_tile = (c.per / 4 + 255) / 256;
+  if (blocks_per_tile * n_tiles > 0x7FFFFFFF) return GSKYHIP_E_ARG;
+  if (png_begin(c, 1)) return GSKYHIP_E_HIP;
+  hipLaunchKernelGGL(png_index_rows_kernel, dim3((unsigned)(blocks_per_tile * n_tiles)), dim3(256), 0, c.s, index,
+                     tile_stride, row_stride, c.d_wh, (int)blocks_per_tile, c.per, c.filt);
+  if (hipGetLastError() != hipSuccess) return GSKYHIP_E_HIP;
+  return png_finish(c);
+}
+
+int gskyhip_encode_png_indexed_host(const uint8_t *index, int w, int h, const uint8_t *ramp, int fixed_only,
+                                    uint8_t *out, int64_t cap, int64_t *out_len) {
+  if (!index || !out || !out_len || w <= 0 || h <= 0 || cap < 0 || (int64_t)h * (1 + (int64_t)w) > (1ll << 30))
+    return GSKYHIP_E_ARG;
+  try {
+    const int stride = 1 + w;
+    const int64_t n = (int64_t)h * stride;
+    std::vector<uint8_t> rows((size_t)n), pal;
+    for (int y = 0; y < h; y++) {
+      rows[(size_t)y * stride] = 0;
+      std::memcpy(rows.data() + (size_t)y * stride + 1, index + (size_t)y * w, (size_t)w);
+    }
+    std::vector<uint8_t> z((size_t)png_deflate_cap(n));
+    int64_t zn = 0;
+    if (deflate::encode_rows_host(rows.data(), h, stride, 1, fixed_only ? 1 : 0, z.data(), (int64_t)z.size(), &zn))
+      return GSKYHIP_E_ARG;
+    png_palette_chunks(ramp, pal);
+    *out_len = 8 + 25 + (int64_t)pal.size() + (zn + 32767) / 32768 * 12 + zn + 12;
+    if (*out_len > cap) return GSKYHIP_E_ARG;
+    const size_t wrote = png_frame(z.data(), (size_t)zn, w, h, 1, &pal, out, (size_t)cap, nullptr);
+    if (!wrote) return GSKYHIP_E_ARG;
+    *out_len = (int64_t)wrote;
+    return 0;
+  } catch (...) {
+    return GSKYHIP_E_ARG;
+  }
 }
 
 // ---- GeoTIFF (EncodeGdalOpen / EncodeGdal, utils/ogc_encoders.go:277-450)

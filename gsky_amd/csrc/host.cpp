@@ -1362,6 +1362,25 @@ int gskyhip_render_tile_info(void *workspace, int n_tiles, int n_pairs, int max_
   return 0;
 }
 
+int gskyhip_render_canvas_info(void *workspace, int n_tiles, int n_pairs, int max_tile_height, int32_t *info_out,
+                               double *nodata_out, void *stream) {
+  if (n_tiles < 0 || n_pairs < 0 || (n_tiles > 0 && (!workspace || !info_out || !nodata_out))) return GSKYHIP_E_ARG;
+  if (n_tiles == 0) return 0;
+  const int64_t off = gsky::render_tile_plans_offset(n_tiles, n_pairs, max_tile_height);
+  std::vector<TilePlan> tp((size_t)n_tiles);
+  if (hipMemcpyAsync(tp.data(), (char *)workspace + off, sizeof(TilePlan) * n_tiles, hipMemcpyDeviceToHost,
+                     (hipStream_t)stream) != hipSuccess ||
+      hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
+    return GSKYHIP_E_HIP;
+  for (int t = 0; t < n_tiles; t++)
+    for (int k = 0; k < 4; k++) {
+      info_out[8 * t + k] = tp[t].created[k];
+      info_out[8 * t + 4 + k] = tp[t].dtype[k];
+      nodata_out[4 * t + k] = tp[t].nodata[k];
+    }
+  return 0;
+}
+
 int gskyhip_render_touched(void *workspace, int n_tiles, int n_pairs, int max_tile_height, int64_t *bytes_out,
                            void *stream) {
   if (n_tiles < 0 || n_pairs < 0 || !bytes_out || (n_pairs > 0 && !workspace)) return GSKYHIP_E_ARG;

@@ -1,5 +1,6 @@
 """Output codecs over the C-ABI (include/gskyhip.h): EncodePNG's png.Encode
-(utils/ogc_encoders.go:139) for batches of RGBA tiles rendered into HBM, and
+(utils/ogc_encoders.go:139) for batches of RGBA tiles rendered into HBM, the
+opt-in indexed-colour PNG of one-band tiles (encode_png_indexed), and
 the WCS GeoTIFF of EncodeGdalOpen / EncodeGdal (ogc_encoders.go:277-450)."""
 from __future__ import annotations
 
@@ -36,6 +37,84 @@ def encode_png(rgba: torch.Tensor, sizes: Optional[Sequence[Tuple[int, int]]] = 
                                out.ctypes.data_as(C.c_void_p), cap, lens.ctypes.data_as(C.c_void_p), threads,
                                C.c_void_p(torch.cuda.current_stream().cuda_stream)), "encode_png")
     return [out[t * cap:t * cap + int(lens[t])].tobytes() for t in range(n)]
+
+
+def _ramp_of(palette, who: str) -> Optional[np.ndarray]:
+    """The 256 x RGBA ramp of a Palette (GradientRGBAPalette), of a 256 x 4
+    array as it is, or None (grey)."""
+    if palette is None:
+        return None
+    if hasattr(palette, "colours"):
+        from .raster import gradient_rgba_palette
+        return np.ascontiguousarray(gradient_rgba_palette(palette))
+    ramp = np.asarray(palette)
+    if ramp.shape != (256, 4) or ramp.dtype != np.uint8:
+        raise ValueError("%s: palette must be a Palette, a (256, 4) uint8 array or None" % who)
+    return np.ascontiguousarray(ramp)
+
+
+def encode_png_indexed(index: torch.Tensor, palette=None, sizes: Optional[Sequence[Tuple[int, int]]] = None,
+                       n_threads: Optional[int] = None) -> List[bytes]:
+    """Indexed-colour PNG bytes (colour type 3, gskyhip_encode_png_indexed) of
+    every tile of a batch of ByteRasters (n_tiles, max_h, max_w) uint8 on the
+    device, 0xFF = nodata, e.g. TileBatch.render_bytes(): what encode_png
+    gives for the RGBA of the same rasters decodes to the same pixels, from a
+    quarter of the bytes through Deflate.  Opt-in and beyond the reference,
+    which always writes truecolour.  palette: a Palette, the 256 x 4 ramp of
+    gradient_rgba_palette, or None for a grey layer; sizes (width, height) per
+    tile (default the full slot), e.g. TileBatch.tile_sizes."""
+    if index.dim() != 3 or index.dtype != torch.uint8 or not index.is_cuda:
+        raise ValueError("encode_png_indexed: (n, H, W) uint8 device tensor expected")
+    if index.stride(2) != 1 or index.stride(1) < index.shape[2] or index.stride(0) < index.stride(1) * index.shape[1]:
+        index = index.contiguous()   # (padded rows and slots are taken as they are)
+    n, mh, mw = index.shape
+    ramp = _ramp_of(palette, "encode_png_indexed")
+    if sizes is None:
+        sizes = [(mw, mh)] * n
+    wh = np.ascontiguousarray(np.asarray(sizes, np.int32).reshape(n, 2))
+    L = lib()
+    ws = torch.empty(max(1, int(L.gskyhip_png_indexed_workspace_size(n, mw, mh))), dtype=torch.uint8,
+                     device=index.device)
+    cap = int(max(L.gskyhip_png_indexed_bound(int(w), int(h)) for w, h in wh)) if n else 0
+    out = np.empty(max(1, n * cap), np.uint8)
+    lens = np.zeros(max(1, n), np.int64)
+    threads = n_threads or max(1, min(16, os.cpu_count() or 1))
+    with torch.cuda.device(index.device):
+        check(L.gskyhip_encode_png_indexed(C.c_void_p(index.data_ptr()), n, mw, mh, index.stride(0) if n else 0,
+                                           index.stride(1), wh.ctypes.data_as(C.c_void_p),
+                                           ramp.ctypes.data_as(C.c_void_p) if ramp is not None else None,
+                                           C.c_void_p(ws.data_ptr()), ws.numel(), out.ctypes.data_as(C.c_void_p),
+                                           cap, lens.ctypes.data_as(C.c_void_p), threads,
+                                           C.c_void_p(torch.cuda.current_stream(index.device).cuda_stream)),
+              "encode_png_indexed")
+    return [out[t * cap:t * cap + int(lens[t])].tobytes() for t in range(n)]
+
+
+def png_indexed_bound(width: int, height: int) -> int:
+    """gskyhip_png_indexed_bound: the most bytes of an indexed PNG of that size (0: bad size)."""
+    return int(lib().gskyhip_png_indexed_bound(int(width), int(height)))
+
+
+def encode_png_indexed_host(index: np.ndarray, palette=None, fixed_only: bool = False) -> bytes:
+    """encode_png_indexed of one host tile, an (h, w) uint8 array
+    (gskyhip_encode_png_indexed_host; no device, no HIP call): the PNG the
+    device path writes for it, byte for byte.  fixed_only: fixed Huffman codes
+    only, as GSKYHIP_PNG_FIXED=1."""
+    index = np.asarray(index)
+    if index.ndim != 2 or index.dtype != np.uint8 or index.size == 0:
+        raise ValueError("encode_png_indexed_host: a non-empty (h, w) uint8 array expected")
+    index = np.ascontiguousarray(index)
+    h, w = index.shape
+    ramp = _ramp_of(palette, "encode_png_indexed_host")
+    L = lib()
+    cap = int(L.gskyhip_png_indexed_bound(w, h))
+    out = np.empty(cap, np.uint8)
+    size = C.c_int64(0)
+    check(L.gskyhip_encode_png_indexed_host(index.ctypes.data_as(C.c_void_p), w, h,
+                                            ramp.ctypes.data_as(C.c_void_p) if ramp is not None else None,
+                                            int(bool(fixed_only)), out.ctypes.data_as(C.c_void_p), cap,
+                                            C.byref(size)), "encode_png_indexed_host")
+    return out[:size.value].tobytes()
 
 
 _TIFF_DTYPES = {torch.uint8: 1, torch.int8: 100, torch.int16: 3, torch.float32: 6}

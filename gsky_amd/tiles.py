@@ -267,6 +267,72 @@ class TileBatch:
             return cv
         return (out, cv) if canvas else out
 
+    def canvas_info(self):
+        """What the last render left in the typed canvases
+        (gskyhip_render_canvas_info; synchronous): per tile and namespace slot
+        (created, value-type code) as an int32 array (n_tiles, 2, 4) and the
+        canvas NoData as a float64 array (n_tiles, 4)."""
+        info = np.zeros((max(1, self.n_tiles), 2, 4), dtype=np.int32)
+        nd = np.zeros((max(1, self.n_tiles), 4), dtype=np.float64)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(lib().gskyhip_render_canvas_info(C.c_void_p(self._ws.data_ptr()), self.n_tiles, self.n_pairs, self.max_h,
+                                               info.ctypes.data_as(C.c_void_p), nd.ctypes.data_as(C.c_void_p),
+                                               stream), "render_canvas_info")
+        return info[: self.n_tiles], nd[: self.n_tiles]
+
+    def render_bytes(self, params: ScaleParams, resample: int = 0) -> torch.Tensor:
+        """The ByteRaster of every tile, (n_tiles, max_h, max_w) uint8 with
+        0xFF = nodata: the merged canvas after utils.Scale, the byte EncodePNG
+        maps through the ramp or to grey -- the input of
+        encode.encode_png_indexed.  One namespace only.  The typed canvases
+        come from render(rgba=False), the bytes from gskyhip_scale: one call
+        over the batch where the tiles share a value type and NoData and the
+        parameters are not an auto-scale, else one call per tile (utils.Scale
+        reduces an auto-scale per raster).  A tile whose canvas no raster
+        reached is all 0xFF; bytes outside a tile's width x height are 0xFF."""
+        if len(self.namespaces) != 1:
+            raise ValueError("Cannot encode other than 1 or 3 namespaces into a PNG: Received %d"
+                             % len(self.namespaces))
+        cv = self.render(params, None, resample, rgba=False)
+        info, nodata = self.canvas_info()
+        H, W, n = self.max_h, self.max_w, self.n_tiles
+        out = torch.full((n, H, W), 0xFF, dtype=torch.uint8, device=self.device)
+        slot = self.slots.index(self.namespaces[0])
+        live = [t for t in range(n) if info[t, 0, slot]]
+        if not live:
+            return out
+        sp = params.c()
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        nbytes = {_lib.BYTE: 1, _lib.SIGNEDBYTE: 1, _lib.INT16: 2, _lib.UINT16: 2, _lib.FLOAT32: 4}
+        autom = params.offset == 0 and params.scale == 0 and params.clip == 0
+        kinds = {(int(info[t, 1, slot]), nodata[t, slot].tobytes()) for t in live}
+        if not autom and len(kinds) == 1:
+            # the whole canvas buffer as one raster: a tile's H * W values lead its 4 * H * W byte slot
+            dt, nd = int(info[live[0], 1, slot]), float(nodata[live[0], slot])
+            per = 4 // nbytes[dt] * H * W
+            tmp = torch.empty((n, per), dtype=torch.uint8, device=self.device)
+            check(lib().gskyhip_scale(C.c_void_p(cv.data_ptr()), dt, n * per, nd, C.byref(sp),
+                                      C.c_void_p(tmp.data_ptr()), stream), "Scale")
+            out = tmp[:, : H * W].reshape(n, H, W).contiguous()
+            # what no raster wrote: tiles never created, slots larger than their tile
+            dead = [t for t in range(n) if not info[t, 0, slot]]
+            if dead:
+                out[torch.tensor(dead, device=self.device)] = 0xFF
+            for t, (w, h) in enumerate(self.tile_sizes):
+                if w < W or h < H:
+                    out[t, h:] = 0xFF
+                    out[t, :, w:] = 0xFF
+            return out
+        for t in live:
+            dt, nd = int(info[t, 1, slot]), float(nodata[t, slot])
+            w, h = self.tile_sizes[t]
+            src = self.canvas_view(cv, t, 0, TYPE_NAMES[dt])[:h, :w].contiguous()
+            dst = torch.empty((h, w), dtype=torch.uint8, device=self.device)
+            check(lib().gskyhip_scale(C.c_void_p(src.data_ptr()), dt, h * w, nd, C.byref(sp),
+                                      C.c_void_p(dst.data_ptr()), stream), "Scale")
+            out[t, :h, :w] = dst
+        return out
+
     # ------------------------------------------------------------------ graphs
     def set_tiles(self, tiles) -> None:
         """New requests of the same shape: every tile's (bbox, width, height)

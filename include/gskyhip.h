@@ -840,6 +840,68 @@ int gskyhip_encode_png(const uint8_t *rgba, int n_tiles, int max_w, int max_h, i
 int gskyhip_png_deflate_rows_host(const uint8_t *rows, int h, int stride, int bpp, int fixed_only, uint8_t *out,
                                   int64_t cap, int64_t *out_len);
 
+/* Indexed-colour PNG (colour type 3) of a batch of one-band tiles in HBM: the
+ * ByteRaster of utils.Scale, one index byte a pixel with 0xFF = nodata, and
+ * the 256 x RGBA ramp of GradientRGBAPalette (gskyhip_gradient_palette) or
+ * NULL for a grey layer.  Beyond the reference, and opt-in: EncodePNG
+ * (ogc_encoders.go:82-142) always expands such a raster to an image.RGBA and
+ * gskyhip_encode_png follows it; this encoder writes the index bytes
+ * themselves, a quarter of the bytes through Deflate, and every decoder gives
+ * the RGBA of the truecolour PNG of the same tile, pixel for pixel.  Go's
+ * png.Encode never sees an image.Paletted here, so byte parity with it is
+ * unpinned; the format is this library's:
+ *   signature, IHDR (w, h, bit depth 8, colour type 3, 0, 0, 0), PLTE, tRNS,
+ *   IDAT chunks of 32768 bytes (the last one shorter), IEND, each with its
+ *   CRC-32;
+ *   PLTE, 256 entries: entry i < 255 is the non-premultiplied RGB of ramp[i]
+ *     (color.NRGBAModel, as gskyhip_encode_png converts a canvas: a = 255 the
+ *     bytes, a = 0 (0, 0, 0), else per channel
+ *     (((c * 0x101) * 0xFFFF) / (a * 0x101) >> 8) & 0xFF), or (i, i, i) for
+ *     grey; entry 255 is (0, 0, 0);
+ *   tRNS, 256 bytes: the alpha of ramp[i], or 255 for grey; entry 255 is 0
+ *     (a nodata pixel is transparent black, ogc_encoders.go:96, 105);
+ *   image data: every row is the filter byte 0 (None; no filter selection)
+ *     and the row's w index bytes;
+ *   zlib stream: gskyhip_encode_png's GPU deflate over those rows with one
+ *     byte a pixel -- one final block, per-tile dynamic Huffman codes where
+ *     they are shorter, else fixed codes, Adler-32 -- GSKYHIP_PNG_FIXED=1 and
+ *     GSKYHIP_PNG_ZLIB=1 honoured alike; tiles of more than 4096 rows go to
+ *     host zlib.
+ * Arguments as gskyhip_encode_png:
+ *   index: dev, tile t row y at index + t*tile_stride + y*row_stride (bytes,
+ *     row_stride >= max_w, tile_stride >= row_stride * max_h);
+ *   sizes: HOST int32 2 per tile {width, height} (<= max_w, max_h);
+ *   ramp: HOST 256 x 4 bytes or NULL; PLTE and tRNS are framed once per call;
+ *   workspace: dev, 8-byte aligned, >= gskyhip_png_indexed_workspace_size;
+ *   png_out: HOST, png_capacity bytes per tile (>= gskyhip_png_indexed_bound
+ *     (w, h)); png_sizes: HOST int64 per tile, the PNG's length.
+ * GSKYHIP_E_ARG before any HIP call for a NULL pointer, a size outside
+ * max_w x max_h, a short stride, capacity or workspace; n_tiles <= 0: 0.
+ * Three-band tiles have no index: they stay with gskyhip_encode_png. */
+int64_t gskyhip_png_indexed_workspace_size(int n_tiles, int max_w, int max_h);
+int64_t gskyhip_png_indexed_bound(int width, int height);
+int gskyhip_encode_png_indexed(const uint8_t *index, int n_tiles, int max_w, int max_h, int64_t tile_stride,
+                               int64_t row_stride, const int32_t *sizes, const uint8_t *ramp, void *workspace,
+                               int64_t workspace_bytes, uint8_t *png_out, int64_t png_capacity,
+                               int64_t *png_sizes, int n_threads, void *stream);
+/* The host twin of gskyhip_encode_png_indexed for one tile (index: HOST,
+ * w * h bytes, rows w apart): the same functions in a loop, no HIP call, so
+ * the PNG the device path writes, byte for byte.  fixed_only: as
+ * GSKYHIP_PNG_FIXED=1.  *out_len is the PNG's length.  GSKYHIP_E_ARG for a
+ * NULL index, out or out_len, w or h <= 0, more than 2^30 bytes of image
+ * data, or a PNG longer than cap (nothing is written to out; *out_len is
+ * still the length needed when the other arguments are good). */
+int gskyhip_encode_png_indexed_host(const uint8_t *index, int w, int h, const uint8_t *ramp, int fixed_only,
+                                    uint8_t *out, int64_t cap, int64_t *out_len);
+
+/* What the last render left in every tile's typed canvases (the canvas_out
+ * of gskyhip_render_tiles, same workspace and sizes): info_out HOST int32 8
+ * per tile = created[4], dtype[4] by namespace slot (a slot no raster reached
+ * is not created and its canvas was never written); nodata_out HOST double 4
+ * per tile, the canvas NoData of each slot.  Synchronises `stream`. */
+int gskyhip_render_canvas_info(void *workspace, int n_tiles, int n_pairs, int max_tile_height,
+                               int32_t *info_out, double *nodata_out, void *stream);
+
 /* EncodeGdalOpen + EncodeGdal for format "geotiff" (utils/ogc_encoders.go:
  * 277-450) of one WCS coverage held in HBM: a BigTIFF with the reference's
  * creation options COMPRESS=PACKBITS, TILED=YES, BIGTIFF=YES,
